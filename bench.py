@@ -2,8 +2,13 @@
 """Benchmark of the hot path: encoder+attention+decoder TRAINING frames/sec on WSJ-shape synthetic fbank batches.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload wsj_base|wsj_deep|wsj_stack2|wsj_paper|timit_tiny|wsj_decode]
-                    [--scaling weak|strong] [--batch B]
+                    [--scaling weak|strong] [--batch B] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds the secondary measurements around it
+(with_h2d, sustained, ragged, strong, the all-reduce alone, roofline + dense_gemm, fbank, decode + beam200, cpu_baseline; the
+--no-* flags and --sustained-seconds select among them).  `--dump-outputs DIR` writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs()), so that two builds can be compared output for output on the same seeded inputs.
 
 A step = forward + backward of the whole recognizer on one minibatch already resident in HBM, the (RCCL) sum
 all-reduce of the flat gradient buffer when N > 1, and the fused optimiser step (clip -> scale -> AdaDelta ->
@@ -331,6 +336,23 @@ def cpu_baseline(cfg, params, B, T, L, workload):
     return out
 
 
+DUMP_CAP = dict(cost_matrix=1 << 20, parameters=7 << 20, gradients=7 << 20)      # float32 elements per file: 60 MiB in all
+
+
+def dump_outputs(out_dir, cm, store):
+    """--dump-outputs: what the timed path computed in its last step, as out_dir/<name>.npy (float32): the cost matrix
+    Trainer.train_step returned (labels x utterances of rank 0), and the store's flat parameter and gradient vectors after that
+    step (ParameterStore.offsets maps names to slices).  An array longer than its DUMP_CAP entry is written as a fixed sample: the
+    elements at the sorted indices numpy.random.RandomState(0).choice(n, cap, replace=False)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in (("cost_matrix", cm), ("parameters", store.flat), ("gradients", store.grad)):
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > DUMP_CAP[name]:
+            a = a.ravel()[numpy.sort(numpy.random.RandomState(0).choice(a.size, DUMP_CAP[name], replace=False))]
+        numpy.save(os.path.join(out_dir, name + ".npy"), numpy.ascontiguousarray(a))
+        log("bench: wrote %s %s (%s)" % (os.path.join(out_dir, name + ".npy"), a.shape, "sampled" if a.size < t.numel() else "whole"))
+
+
 def main(backend=None):
     backend = backend or GpuBackend()
     ap = argparse.ArgumentParser()
@@ -365,7 +387,16 @@ def main(backend=None):
                     help="data parallel: reduce the decoder's gradients while the encoder's BPTT runs (two buckets, Trainer(overlap_allreduce=True))")
     ap.add_argument("--utterances", type=int, default=None, help="wsj_decode: number of utterances (default 1000 = configs[4])")
     ap.add_argument("--streams", type=int, default=None, help="wsj_decode: recognizers (streams) in flight per GPU (default 4 batches; 8 searches with --decode-batch 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements: with_h2d, sustained, ragged, strong, the all-reduce alone, roofline (+ dense_gemm), "
+                         "fbank, decode (+ beam200), cpu_baseline (the --no-* flags and --sustained-seconds select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (cost matrix, parameters and gradients after it) as DIR/<name>.npy, float32")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and args.workload == "wsj_decode":
+        ap.error("--dump-outputs is for the training workloads; wsj_decode has no step outputs to write")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(respawn_under_torchrun(args.gpus))
@@ -420,8 +451,8 @@ def main(backend=None):
     trainer = Trainer(rec, distributed=dist, overlap_allreduce=args.overlap_allreduce, **TRAIN_CONF)
     nsteps = args.steps + args.warmup
     # synthetic global batches, seeded identically on every rank; rank r keeps utterances r::world.  `value` is measured with the
-    # minibatches resident in HBM (the bench contract); the same K steps are then repeated with the minibatches waiting in PINNED
-    # HOST memory and copied per step (four asynchronous copies on the recognizer's stream in front of the step's graph): the
+    # minibatches resident in HBM (the bench contract); with --full the same K steps are then repeated with the minibatches waiting
+    # in PINNED HOST memory and copied per step (four asynchronous copies on the recognizer's stream in front of the step's graph): the
     # H2D-inclusive step of SURVEY.md 8(d), reported beside it as config.with_h2d.
     nstage = min(nsteps, 4)
     staged, staged_host = [], []
@@ -429,7 +460,7 @@ def main(backend=None):
         gb = synthetic.make_batch(cfg, global_batch, T, L, seed=1234 + s, ragged=args.ragged)
         sh = synthetic.shard_batch(gb, rank, world)
         staged.append({k: torch.from_numpy(v).to(dev) for k, v in sh.items()})
-        if dev.type == "cuda":
+        if dev.type == "cuda" and args.full:
             staged_host.append({k: torch.from_numpy(v).pin_memory() for k, v in sh.items()})
     h2d_bytes = sum(v.numel() * v.element_size() for v in staged[0].values())
     # real (unpadded) frames per step over all ranks: every rank holds global_batch/world utterances of the same lengths
@@ -473,6 +504,11 @@ def main(backend=None):
     marks[-1] = t0 + elapsed
     per_step = sorted((b - a) * 1e3 for a, b in zip(marks[:-1], marks[1:]))
     ms_median = per_step[len(per_step) // 2] if len(per_step) % 2 else 0.5 * (per_step[len(per_step) // 2 - 1] + per_step[len(per_step) // 2])
+    # the last timed step's outputs, taken before any --full leg steps the trainer again
+    last_cost = float(cm.sum())
+    assert numpy.isfinite(last_cost), "training diverged in the benchmark"
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, cm, rec.store)
     with_h2d = None
     if staged_host:
         trainer.train_step(staged_host[0], global_batch_size=global_batch)
@@ -518,7 +554,7 @@ def main(backend=None):
     # ---- sustained segment: the same replayed step for several seconds, so that the clocks are those of a long run (the K timed
     # steps above last a fraction of a second on a chip that has just been idle) and samplers with a coarse period see the GPU busy
     sustained = None
-    if backend.measured and args.sustained_seconds > 0:
+    if backend.measured and args.full and args.sustained_seconds > 0:
         n_sus = max(20, int(args.sustained_seconds / max(1e-4, elapsed / args.steps)))
         el, iv = timed(trainer, staged, n_sus, global_batch, 0)
         srt = sorted(iv)
@@ -533,7 +569,7 @@ def main(backend=None):
     # ---- secondary run of SURVEY.md 8(d): the same job on RAGGED minibatches (T_i ~ U{T/2..T}, L_i ~ U{L/2..L}, zero padded to (T, L);
     # utterance 0 of every global batch full length) — real (unpadded) frames per second
     ragged = None
-    if backend.measured and not args.ragged and not args.no_ragged and args.scaling == "weak":
+    if backend.measured and args.full and not args.ragged and not args.no_ragged and args.scaling == "weak":
         rb, rframes = [], 0.0
         for k in range(2):
             gbatch = synthetic.make_batch(cfg, global_batch, T, L, seed=2345 + k, ragged=True)
@@ -580,7 +616,7 @@ def main(backend=None):
     # at 8 GPUs): the same job in the SAME launch as the weak line, and the one-GPU step at that global batch it is measured against
     strong = None
     strong_batches = dict(STRONG_GLOBAL_BATCH, **getattr(backend, "strong_global_batch", {}))
-    if (backend.measured or getattr(backend, "strong_leg", False)) and not args.no_strong and args.scaling == "weak" \
+    if (backend.measured or getattr(backend, "strong_leg", False)) and args.full and not args.no_strong and args.scaling == "weak" \
             and args.workload in strong_batches and not args.ragged and not args.frames and not args.batch:
         GB = strong_batches[args.workload]
         if GB % world == 0:
@@ -637,8 +673,6 @@ def main(backend=None):
                                                  "utterances, 13.5 ms + one 20.9 MB all-reduce, 0.3 ms): DESIGN.md section 5; the chain "
                                                  "floor of 16 utterances per GPU (2 x 2 800 recurrent steps x 1.1 us + decoder + "
                                                  "products = 10.8 ms) bounds this mechanism at 5.3x")
-    last_cost = float(cm.sum())
-    assert numpy.isfinite(last_cost), "training diverged in the benchmark"
     # ---- self-check inputs (all ranks): was any step skipped, did the step replay as a captured graph region
     skipped_local = 1.0 if trainer.step_was_skipped() else 0.0
     regions = list(getattr(rec, "_regions", {}).values())
@@ -670,7 +704,7 @@ def main(backend=None):
 
     # the exchange step alone: ONE sum all-reduce of the flat gradient bucket (RCCL over xGMI on GPUs), timed back to back
     allreduce_ms = None
-    if dist:
+    if dist and args.full:
         g = rec.store.grad
         for _ in range(2):
             torch.distributed.all_reduce(g)
@@ -698,7 +732,7 @@ def main(backend=None):
                        h2d="value: minibatches resident in HBM when the timed region starts (bench contract); with_h2d: the same steps fed from pinned host memory",
                        with_h2d=(dict(with_h2d, value=frames_per_step / (with_h2d["ms_per_step"] * 1e-3)) if with_h2d else None),
                        value_is="steps * frames_per_step / wall time of the K steps (mean); ms_per_step_median = median of the per-step host intervals",
-                       final_cost_per_utterance=last_cost / B, knobs=knobs))
+                       final_cost_per_utterance=last_cost / B, knobs=knobs, full=bool(args.full)))
         if sustained:
             out["sustained"] = sustained
         if ragged:
@@ -716,7 +750,7 @@ def main(backend=None):
                                  whole_step_graph_region=bool(graph_region_ok), steps_skipped=int(skipped_total), cluster_aborts=int(trainer.aborts),
                                  rank_r_holds_utterances_r_mod_world=bool(shards_ok),
                                  cluster_reserve=int(rec.lib.get_knob("cluster_reserve")))
-        if backend.measured:
+        if backend.measured and args.full:
             pr = dominant_kernel_probe(rec, dims, T, B)
             ach = pr["flops"] / pr["launch_s"] / 1e12
             pmc, pmc_why = pmc_record(pr["kernel"] + "@%s" % args.workload) if B == B0 else (None, "PMC record is for the default per-GPU batch")

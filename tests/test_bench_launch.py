@@ -26,7 +26,7 @@ def _run(*flags, workload="toy"):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_launches_two_ranks_by_itself(scaling):
-    out = _run("--gpus", "2", "--scaling", scaling)
+    out = _run("--gpus", "2", "--scaling", scaling, "--full")
     assert out["n_gpus"] == 2 and out["scaling"] == scaling and out["unit"] == "frames/s" and out["value"] > 0
     c = out["config"]
     assert c["collective_world_size"] == 2 and c["collective_backend"] == "gloo" and c["allreduce_ms"] > 0
@@ -44,12 +44,25 @@ def test_single_rank_line_has_no_collective_fields():
     assert out["n_gpus"] == 1 and "collective_world_size" not in out["config"] and out["config"]["global_batch"] == 4
 
 
+def test_plain_run_times_the_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) runs no secondary leg — not even the `strong` one this stand-in backend would run — honours --steps,
+    and --dump-outputs writes the last timed step's cost matrix and the parameters / gradients after it as float32 arrays."""
+    import numpy
+    out = _run("--steps", "3", "--dump-outputs", str(tmp_path), workload="toy_strong128")
+    assert out["steps"] == 3 and out["ms_per_step"] > 0 and out["config"]["full"] is False
+    assert "strong" not in out and out["config"]["with_h2d"] is None
+    got = {n: numpy.load(str(tmp_path / (n + ".npy"))) for n in ("cost_matrix", "parameters", "gradients")}
+    assert all(a.dtype == numpy.float32 and numpy.isfinite(a).all() for a in got.values())
+    assert got["cost_matrix"].shape == (5, 4) and got["parameters"].shape == got["gradients"].shape
+    assert abs(float(got["cost_matrix"].sum()) / 4 - out["config"]["final_cost_per_utterance"]) < 1e-4 * max(1.0, abs(out["config"]["final_cost_per_utterance"]))
+
+
 def test_world_8_launch_is_boring():
     """The first 8-rank run (round-5 verdict, ask 6): `bench.py --gpus 8` as the driver calls it, eight gloo ranks on the emulator —
     the collective spans exactly eight ranks, every rank was fed utterances r::8 of the global minibatch (fingerprints gathered and
     compared on rank 0), the weak line counts all ranks' frames, and the `strong` sub-object shards global batch 128 into 16 per
     rank and carries BOTH one-GPU forms it is quoted against."""
-    out = _run("--gpus", "8", workload="toy_strong128")
+    out = _run("--gpus", "8", "--full", workload="toy_strong128")
     c, chk = out["config"], out["self_check"]
     assert out["n_gpus"] == 8 and out["scaling"] == "weak"
     assert c["collective_world_size"] == 8 and c["parallelism"] == "dp8" and c["per_gpu_batch"] == 4 and c["global_batch"] == 32
