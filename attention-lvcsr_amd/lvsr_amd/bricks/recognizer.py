@@ -8,6 +8,7 @@ What Theano derived symbolically is explicit here: `cost(...)` is the forward pa
 size afterwards; `cost_and_gradients` does the same).
 """
 import contextlib
+import logging
 import os
 
 import numpy
@@ -17,6 +18,8 @@ from .. import spec
 from ..params import ParameterStore, Workspace
 from . import Encoder, SpeechBottom
 from .generator import SequenceGenerator
+
+logger = logging.getLogger(__name__)
 
 
 class SpeechRecognizer(object):
@@ -52,6 +55,10 @@ class SpeechRecognizer(object):
         # hipGraph capture cannot run on the legacy null stream: the hot path owns a side stream
         self.stream = torch.cuda.Stream(self.device) if self.device.type == "cuda" else None
         self.beam_size = None
+        # adaptive weight noise: log-variances found in a loaded checkpoint (parameter name -> array), set aside for a noisy trainer,
+        # and the noise state of the trainer attached now (its log-variances go into save_params), lvsr_amd/weight_noise.py
+        self.noise_values = {}
+        self.weight_noise = None
         if lm_config.get("path"):                                  # recognizer.py:322-337
             from ..lm import language_model_from_config
             self.set_language_model(language_model_from_config(lm_config, net_kwargs.get("character_map"), self.device,
@@ -89,13 +96,33 @@ class SpeechRecognizer(object):
         self.store.set_values(values)
 
     def load_params(self, path):
-        """recognizer.py:408-412: load a Blocks checkpoint (tar with `_parameters`) or an .npz by parameter name."""
+        """recognizer.py:408-412: load a Blocks checkpoint (tar with `_parameters`) or an .npz by parameter name.  The log-variances
+        of adaptive noise (`/adaptive_noise.*`, lvsr/main.py:462-470) are set aside in `noise_values` for a noisy trainer; without
+        one they are ignored, as Blocks' Model.set_parameter_values logs and skips unknown names (libs/blocks/blocks/model.py:137-141)."""
         from ..checkpoint import load_parameters
-        self.store.set_values(load_parameters(path))
+        from ..weight_noise import is_noise_name, param_name
+        values, noise = {}, {}
+        for k, v in load_parameters(path).items():
+            if not is_noise_name(k):
+                values[k] = v
+                continue
+            p = param_name(k)
+            if p not in self.store.shapes or tuple(numpy.shape(v)) != tuple(self.store.shapes[p]):
+                raise ValueError("%s does not match a parameter of this recognizer (shape %s)" % (k, numpy.shape(v)))
+            noise[p] = numpy.asarray(v, numpy.float32)
+        self.store.set_values(values)
+        self.noise_values = noise
+        if noise:
+            logger.info("%s: %d adaptive-noise log-variances set aside (used by a trainer with adaptive noise)", path, len(noise))
 
     def save_params(self, path, extra=None):
+        """Blocks-style checkpoint of the parameters; while a trainer with adaptive noise is attached, the current log-variances
+        too, under the reference's names (lvsr_amd/weight_noise.py)."""
         from ..checkpoint import save_parameters
-        save_parameters(path, self.store.get_values(), extra=extra)
+        values = self.store.get_values()
+        if self.weight_noise is not None:
+            values.update(self.weight_noise.ls2_values())
+        save_parameters(path, values, extra=extra)
 
     def initialize(self, initialization, seed=1):
         """Apply the reference's `initialization:` config section (lvsr/main.py:225-232): brick paths mapped to
@@ -220,14 +247,16 @@ class SpeechRecognizer(object):
         assert all(k.startswith("/recognizer/generator") == (o >= first) for k, (o, n) in offs.items()), "decoder parameters are not a tail"
         return first, self.store.flat.numel() - first
 
-    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None):
+    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None, head=None):
         """One training forward+backward on a batch dict in the reference's layout.
         Returns the cost matrix (L,B) on the device; gradients of its sum are in self.store.grad.
         `tail` (optional callable, described by the hashable `tail_key`) enqueues more work behind the backward pass — the
         optimiser step — inside the same graph region: the whole step is then ONE hipGraph launch per minibatch shape.
         `between` (optional callable, data parallelism with overlapped exchange): called — eagerly, outside any graph region — when
         the decoder's gradients are final and before the encoder's backward pass is enqueued; the step is then TWO graph regions
-        (forward + decoder backward | encoder backward [+ tail])."""
+        (forward + decoder backward | encoder backward [+ tail]).
+        `head` (optional callable, described by `tail_key` as well) enqueues work in front of the forward pass inside the (first)
+        graph region: the noisy weights of adaptive noise."""
         with self._on_stream():
             x, xm, y, ym = self._stage(batch["recordings"], batch.get("recordings_mask"), batch["labels"],
                                        batch.get("labels_mask"))
@@ -237,10 +266,13 @@ class SpeechRecognizer(object):
             plain = region and self.use_graph and not self.encoder.overlap
             if between is not None:
                 def first_half():
+                    if head is not None:
+                        head()
                     cm = self._forward(x, xm, y, ym)
                     return cm, self._backward_decoder()
 
-                cm, d_encoded = self.lib.region(self, ("train_step_fwd_dec",) + shape_key, x, enabled=plain, volatile=volatile).run(first_half)
+                key1 = ("train_step_fwd_dec",) + shape_key + ((tail_key,) if head is not None else ())
+                cm, d_encoded = self.lib.region(self, key1, x, enabled=plain, volatile=volatile).run(first_half)
                 between()
 
                 def second_half():
@@ -253,6 +285,8 @@ class SpeechRecognizer(object):
                 return cm
 
             def enqueue():
+                if head is not None:
+                    head()
                 cm = self._forward(x, xm, y, ym)
                 self.backward()
                 if tail is not None:

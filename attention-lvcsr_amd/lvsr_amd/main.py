@@ -69,10 +69,11 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
     from .config import Configuration
     log = [] if log is None else log
     reg = dict(config.get("regularization") or {})
-    unbuilt = [k for k in ("dropout", "noise", "adaptive_noise") if reg.get(k)] + \
+    unbuilt = [k for k in ("dropout", "noise") if reg.get(k)] + \
               [k for k in ("penalty_coof", "decay") if (reg.get(k) or 0) > 0]
-    if unbuilt:        # lvsr/main.py:395-470 rewrites the Theano graph for these; silently ignoring them would change the recipe
-        raise NotImplementedError("regularization.%s is not built (only max_norm is)" % ", regularization.".join(unbuilt))
+    if unbuilt:        # lvsr/main.py:395-424 rewrites the Theano graph for these; silently ignoring them would change the recipe
+        raise NotImplementedError("regularization.%s is not built (only max_norm and adaptive_noise are)"
+                                  % ", regularization.".join(unbuilt))
     train_conf, mon = dict(config.get("training", {})), dict(config.get("monitoring", {}))
     net = dict(config["net"])
     kw = Configuration.net_kwargs(config, data.num_features(), data.num_labels, eos_label=data.eos_label) \
@@ -88,7 +89,9 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
     if params:
         rec.load_params(params)
     rank, world, barrier = _dist_state(distributed)
-    trainer = Trainer.from_config(rec, train_conf, config.get("regularization"), distributed=world > 1 or bool(distributed))
+    # adaptive noise divides its model cost by the size of the training set (lvsr/main.py:434)
+    trainer = Trainer.from_config(rec, train_conf, config.get("regularization"), distributed=world > 1 or bool(distributed),
+                                  num_examples=data.datasets["train"].num_examples)
     root, ext = os.path.splitext(save_path)
     best_ll, best_per, best_epoch = float("inf"), float("inf"), 0
     num_batches, num_epochs = train_conf.get("num_batches"), train_conf.get("num_epochs")
@@ -136,6 +139,10 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
             iterations += 1
             row = dict(iterations_done=iterations, epochs_done=epoch, train_cost=float(cm.sum()) / int(batch["labels"].shape[1]),
                        total_gradient_norm=trainer.gradient_norm(), gradient_norm_threshold=trainer.gradient_threshold())
+            if trainer.noise is not None:
+                # NoiseBrick (lvsr/graph.py:41-54): train_cost = task cost + model cost; the observables of lvsr/main.py:447-456
+                row.update(trainer.noise_stats())
+                row["train_cost"] += row["model_cost"]
             costs.append(row["train_cost"])
             log.append(row)
             if not numpy.isfinite(row["total_gradient_norm"]):        # FinishAfter(...).add_condition(_gradient_norm_is_none)

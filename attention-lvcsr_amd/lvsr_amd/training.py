@@ -44,10 +44,17 @@ class Trainer(object):
     def __init__(self, recognizer, gradient_threshold=None, rules=("momentum",), scale=0.1, momentum=0.0,
                  decay_rate=0.95, epsilon=1e-8, max_norm=0.0, max_norm_exclude_lookup=False, nonfinite_scaler=0.0,
                  burn_in_steps=0, adaptive_clipping=None, process_group=None, distributed=None, dp_region=True,
-                 overlap_allreduce=False):
+                 overlap_allreduce=False, adaptive_noise=None, num_examples=None):
         """Keywords = `training:` / `regularization:` keys of the reference's config (lvsr/main.py:480-519).
         `adaptive_clipping`: None, True or dict(decay_rate=0.998, burnin_period=500) — the AdaptiveClipping extension the
-        reference's `train()` always installs on top of `gradient_threshold` (lvsr/main.py:616-619)."""
+        reference's `train()` always installs on top of `gradient_threshold` (lvsr/main.py:616-619).
+        `adaptive_noise`: None, True or dict(model_cost_coefficient=1.0, init_sigma=1e-6, seed=None) — adaptive weight noise
+        (lvsr/main.py:425-456, lvsr_amd/weight_noise.py); it needs `num_examples`, the size of the training set.  The step rules then
+        run over theta = [means | log-variances] (max_norm on WEIGHT-role means only) and `store.flat` holds the means between steps."""
+        from .weight_noise import settings as noise_settings
+        noise_conf = noise_settings(adaptive_noise)
+        if noise_conf is not None and num_examples is None:
+            raise ValueError("adaptive_noise needs num_examples (the number of examples of the training set, lvsr/main.py:434)")
         self.rec = recognizer
         self._token = recognizer.lib.unique_token()        # names this trainer's buffers in graph-region keys
         st = recognizer.store
@@ -56,7 +63,8 @@ class Trainer(object):
                          use_adadelta=int("adadelta" in rules), learning_rate=float(scale), momentum=float(momentum),
                          decay_rate=float(decay_rate), epsilon=float(epsilon), max_norm=float(max_norm or 0.0),
                          remove_not_finite=1, nonfinite_scaler=float(nonfinite_scaler))
-        n = st.flat.numel()
+        total = st.flat.numel()
+        n = 2 * total if noise_conf is not None else total          # adaptive noise: the rules cover [means | log-variances]
         z = lambda: torch.zeros(n, dtype=torch.float32, device=dev)
         self.velocity = z() if self.conf["use_momentum"] else None
         self.ms_step = z() if self.conf["use_adadelta"] else None
@@ -71,9 +79,16 @@ class Trainer(object):
             if flag:
                 max_cols = max(max_cols, cols)
             seg.append([off, rows, cols, flag])
+        if noise_conf is not None:                  # the log-variances: tensors of their own, never max-norm clipped
+            seg += [[off + total, rows, cols, 0] for off, rows, cols, _ in list(seg)]
         self.max_cols = max_cols
         self.segments = torch.tensor(seg, dtype=torch.int64, device=dev)
         self.segflag = torch.zeros(len(seg), dtype=torch.int32, device=dev)
+        self.noise = None
+        if noise_conf is not None:
+            from .weight_noise import WeightNoise
+            self.noise = WeightNoise(recognizer, self.segments[: len(st.offsets)], num_examples, **noise_conf)
+            recognizer.weight_noise = self.noise          # save_params writes the log-variances while this trainer is attached
         self.scratch = torch.zeros(2 + 256, dtype=torch.float32, device=dev)
         self.clip_state = None
         if adaptive_clipping or burn_in_steps:
@@ -117,9 +132,12 @@ class Trainer(object):
         self.steps_done = 0
 
     @classmethod
-    def from_config(cls, recognizer, training, regularization=None, adaptive_clipping=True, **kw):
-        """Build the step rules the way lvsr/main.py:480-519 reads `config['training']` / `config['regularization']`."""
+    def from_config(cls, recognizer, training, regularization=None, adaptive_clipping=True, num_examples=None, **kw):
+        """Build the step rules the way lvsr/main.py:480-519 reads `config['training']` / `config['regularization']`;
+        `regularization.adaptive_noise` is on when truthy (lvsr/main.py:426), with `num_examples` of the training set."""
         reg = regularization or {}
+        if reg.get("adaptive_noise"):
+            kw.update(adaptive_noise=reg["adaptive_noise"], num_examples=num_examples)
         return cls(recognizer, gradient_threshold=training.get("gradient_threshold"), rules=tuple(training.get("rules", ["momentum"])),
                    scale=training.get("scale", 0.1), momentum=training.get("momentum", 0.0),
                    decay_rate=training.get("decay_rate", 0.95), epsilon=training.get("epsilon", 1e-8),
@@ -137,17 +155,26 @@ class Trainer(object):
                 out[name] = t.detach().cpu().numpy()
         if self.clip_state is not None:
             out["clip_state"] = self.clip_state.detach().cpu().numpy()
-        out["layout"] = numpy.array(["%s:%d:%d" % (n, o, c) for n, (o, c) in self.rec.store.offsets.items()])
+        if self.noise is not None:
+            out["noise_counter"] = self.noise.counter.detach().cpu().numpy()
+        out["layout"] = numpy.array(self._layout())
         return out
 
-    def load_state_dict(self, state):
+    def _layout(self):
+        """The layout record of state_dict: the parameter layout, and whether the accumulators cover the log-variances too."""
         layout = ["%s:%d:%d" % (n, o, c) for n, (o, c) in self.rec.store.offsets.items()]
-        if "layout" in state and [str(x) for x in state["layout"]] != layout:
-            raise ValueError("training state was saved for another parameter layout")
+        return layout + (["adaptive_noise:%d" % self.noise.n] if self.noise is not None else [])
+
+    def load_state_dict(self, state):
+        if "layout" in state and [str(x) for x in state["layout"]] != self._layout():
+            raise ValueError("training state was saved for another parameter layout (or with adaptive noise %s)"
+                             % ("off" if self.noise is not None else "on"))
         for name in ("velocity", "ms_step", "ms_dx", "clip_state"):
             t = getattr(self, name)
             if t is not None and name in state:
                 t.copy_(torch.as_tensor(numpy.asarray(state[name])).to(t.dtype))
+        if self.noise is not None and "noise_counter" in state:
+            self.noise.counter.copy_(torch.as_tensor(numpy.asarray(state["noise_counter"])).to(torch.int64))
 
     def gradient_threshold(self):
         """The StepClipping threshold in force for the next step (moves when adaptive clipping is on)."""
@@ -156,6 +183,12 @@ class Trainer(object):
     def gradient_norm(self):
         """L2 norm of the (scaled, all-reduced) gradient of the last step: the reference's `total_gradient_norm`."""
         return float(self.scratch[0])
+
+    def noise_stats(self):
+        """Adaptive noise: dict(model_cost, model_prior_mean, model_prior_variance) of the last step (synchronises)."""
+        if self.noise is None:
+            raise ValueError("this trainer runs without adaptive noise")
+        return self.noise.observables()
 
     def _enqueue_guard(self):
         """Behind the backward pass: store.guard[0] = number of persistent cluster launches of this step that gave up waiting (the
@@ -169,11 +202,17 @@ class Trainer(object):
 
     def _enqueue_optimizer(self, global_batch_size):
         st, lib = self.rec.store, self.rec.lib
-        a = lib.make("lvsr_opt_args", param=st.flat, grad=st.grad, velocity=self.velocity, ms_step=self.ms_step,
+        param, grad, scale = st.flat, st.grad, 1.0 / float(global_batch_size)
+        if self.noise is not None:        # the gradient rewrite, then the rules over [means | log-variances]
+            self.noise.enqueue_grad(st.grad, scale)
+            param, grad, scale = self.noise.theta, self.noise.gtheta, 1.0
+        a = lib.make("lvsr_opt_args", param=param, grad=grad, velocity=self.velocity, ms_step=self.ms_step,
                      ms_dx=self.ms_dx, step=self.step_buf, segments=self.segments, segflag=self.segflag,
-                     scratch=self.scratch, n=st.flat.numel(), nseg=int(self.segments.shape[0]), max_cols=self.max_cols,
-                     grad_scale=1.0 / float(global_batch_size), clip_state=self.clip_state, guard=st.guard, **self.conf)
+                     scratch=self.scratch, n=param.numel(), nseg=int(self.segments.shape[0]), max_cols=self.max_cols,
+                     grad_scale=scale, clip_state=self.clip_state, guard=st.guard, **self.conf)
         lib.call("lvsr_opt_step", lib.stream_for(st.flat), ctypes.byref(a))
+        if self.noise is not None:
+            self.noise.publish()          # store.flat <- the means (a skipped step included)
         if self._skip_host is not None:
             self._skip_host.copy_(self.scratch[3:4], non_blocking=True)
 
@@ -232,6 +271,8 @@ class Trainer(object):
             lib.set_knob("cluster_reserve", self._overlap_reserve_before)
             self._overlap_reserve_before = None
         self._forget_graphs()
+        if self.noise is not None and getattr(self.rec, "weight_noise", None) is self.noise:
+            self.rec.weight_noise = None
 
     def __enter__(self):
         return self
@@ -307,6 +348,10 @@ class Trainer(object):
         if ref.is_cuda and self._comm is not None:
             torch.cuda.current_stream(ref.device).wait_stream(self._comm)
 
+    def _noise_key(self):
+        """What the head / rewrite of adaptive noise add to a step's graph-region key (nothing without it)."""
+        return () if self.noise is None else (self._token,) + self.noise.key()
+
     def apply_gradients(self, global_batch_size):
         rec, st = self.rec, self.rec.store
         with rec._on_stream():
@@ -324,6 +369,13 @@ class Trainer(object):
         under data parallelism it is obtained by reducing the shard sizes."""
         B_local = int(batch["labels"].shape[1])
         self._before_step()
+        head = None
+        if self.noise is not None:
+            # the head of the step writes the noisy weights into store.flat: cached packs of the weights must be rebuilt
+            self.rec.store.version += 1
+
+            def head():
+                self.noise.enqueue_sample()
         if self.distributed:
             if global_batch_size is None:
                 # shards may differ in size (a global batch that does not divide over the ranks): the divisor of the summed
@@ -338,7 +390,8 @@ class Trainer(object):
                 def reduce_decoder_bucket():
                     with rec._on_stream():
                         self._all_reduce(st.grad[off: off + cnt], wait=False)
-                cm = rec.cost_and_gradients(batch, region=self.dp_region, between=reduce_decoder_bucket)
+                cm = rec.cost_and_gradients(batch, region=self.dp_region, between=reduce_decoder_bucket, head=head,
+                                            tail_key=self._noise_key())
                 with rec._on_stream():
                     self._enqueue_guard()
                     self._all_reduce(st.grad_bucket[: 4 + off], wait=False)          # [guard | encoder gradients]
@@ -346,14 +399,14 @@ class Trainer(object):
                     self._enqueue_optimizer(global_batch_size)
                     st.version += 1
                 return cm
-            cm = self.rec.cost_and_gradients(batch, region=self.dp_region)
+            cm = self.rec.cost_and_gradients(batch, region=self.dp_region, head=head, tail_key=self._noise_key())
             self.apply_gradients(global_batch_size)
             return cm
         gbs = global_batch_size if global_batch_size is not None else B_local
-        tail_key = ("opt", self._token, float(gbs), tuple(sorted(self.conf.items())))
+        tail_key = ("opt", self._token, float(gbs), tuple(sorted(self.conf.items()))) + self._noise_key()
         def tail():
             self._enqueue_guard()
             self._enqueue_optimizer(gbs)
-        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key)
+        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key, head=head)
         self.rec.store.version += 1
         return cm

@@ -387,6 +387,45 @@ int lvsr_opt_step(void* stream, const lvsr_opt_args* a);
  * persistent cluster launches of a step (first int of their workspaces), collected behind the backward pass. */
 int lvsr_guard_collect(void* stream, const int* const* words, int n, float* out);
 
+/* ---- adaptive weight noise (Graves, NIPS 2011; lvsr/graph.py:71-249, wired at lvsr/main.py:425-456) ------------------------
+ * Every parameter p is a Gaussian: mean mu (the parameter) and log-variance ls2, s2 = exp(ls2 * 2048).  A training step runs on
+ * noisy weights mu + z * sqrt(s2), z ~ N(0,1), and its gradients are rewritten with the model cost of the prior
+ * N(prior_u, prior_s2) fitted to all parameters.  mu, ls2, noisy and the two halves of gtheta share the parameter store's flat
+ * layout (n floats, tensors 16-byte aligned); `segments` = the store's tensors (offset, rows, cols, flags): padding is never read,
+ * and only gtheta's padding is written (zeros).
+ * Noise stream: Philox4x32-10, key (seed mod 2^32, seed >> 32), counter (q mod 2^32, q >> 32, c mod 2^32, c >> 32) for element i
+ * of step c with q = i >> 2; uniforms u_j = (2 (x_j >> 9) + 1) 2^-24; Box-Muller pairs (u0,u1) -> z0,z1 and (u2,u3) -> z2,z3;
+ * element i takes z[i & 3].
+ * stats (double, 8 + 4 * 1024): [0] sum mu, [1] sum mu^2, [2] sum s2, [3] sum ls2, [4] prior_u, [5] prior_s2 (both rounded to
+ * float32, lvsr/graph.py:185-197), [6] model cost c/N * (...) (:205-212), [7] number of noisy parameters; [8 + 4 b + k]: partial
+ * sum k of work-group b of the sampler. */
+typedef struct lvsr_wnoise_args {
+    const float* mu; const float* ls2;    /* (n) means and log-variances */
+    float* noisy;                         /* (n) out (lvsr_wnoise_sample): the weights the step runs on */
+    const long long* segments;            /* (nseg,4) the store's tensors: offset, rows, cols, flags (flags are not read) */
+    int nseg, pad0;
+    long long n;
+    long long seed;                       /* Philox key (64 bits) */
+    long long* counter;                   /* device: step counter c, read by the sampler, advanced by lvsr_wnoise_grad */
+    double* stats;                        /* device: see above */
+    const float* grad;                    /* (n) d(sum cost) at the noisy weights (after any all-reduce) */
+    float grad_scale, pad1;               /* 1 / global batch size */
+    double coef;                          /* model_cost_coefficient */
+    double num_examples;                  /* N: examples of the training set */
+    float* gtheta;                        /* (2n) out (lvsr_wnoise_grad): [d/dmu | d/dls2] */
+} lvsr_wnoise_args;
+/* Head of a noisy step: noisy = mu + z sqrt(s2) with s2 = expf(ls2 * 2048) in float32 (not clamped: a non-finite value reaches
+ * RemoveNotFinite, as in the reference); the float64 sums in a fixed order, then prior_u, prior_s2 and the model cost. */
+int lvsr_wnoise_sample(void* stream, const lvsr_wnoise_args* a);
+/* Tail of a noisy step (after the all-reduce), g = grad * grad_scale (lvsr/graph.py:235-247, prior_u / prior_s2 constants):
+ *   gtheta[i]     = c (mu - prior_u) / (N prior_s2) + g
+ *   gtheta[n + i] = (c 0.5 / N 2048) (s2 / prior_s2 - 1) + (0.5 2048) s2 g^2
+ * and *counter += 1 (the next step draws new noise; a replayed graph advances it too). */
+int lvsr_wnoise_grad(void* stream, const lvsr_wnoise_args* a);
+/* Test hook: the sampler's stream for Philox blocks q = first .. first + nblocks - 1 (64-bit, wrapping) of step `counter`:
+ * z[4 b + j] = the normal of element 4 q + j, raw[4 b + j] = the Philox word x_j (raw may be NULL). */
+int lvsr_philox_normal(void* stream, long long seed, long long counter, long long first, long long nblocks, float* z, unsigned* raw);
+
 /* Generation-time readout + emitter of n rows in one launch (one work-group per row):
  * Readout.readout (libs/blocks/blocks/bricks/sequence_generators.py:614-619) with the post-merge stack of
  * lvsr/bricks/recognizer.py:298-320, then SoftmaxEmitter.costs (:788-791) or, with lm_add, ShallowFusionReadout + LMEmitter
