@@ -274,10 +274,10 @@ class Encoder(object):
         assert all(k.startswith("/recognizer/encoder/") == (lo <= o < hi) for k, (o, n) in offs.items()), "encoder parameters are not one range"
         return lo, min(hi, self.store.grad.numel()) - lo
 
-    def _backward_in_passes(self, cols, d_encoded, need_input_grad):
+    def _backward_in_passes(self, cols, d_encoded, need_input_grad, group=None):
         """Every pass writes its own encoder gradients (the kernels and products overwrite); they are summed in a side buffer
-        between the passes (lvsr_copy2d_many with beta = 1).  The pending grouped launch (the decoder's weight-gradient products, if
-        the caller opened one) is flushed with the first pass."""
+        between the passes (lvsr_copy2d_many with beta = 1).  Every pass ends with a grouped launch of its own; what the caller's
+        `group` already holds (the decoder's weight-gradient products) goes out with the first pass."""
         d, lib, ws = self.d, self.lib, self.ws
         dy = d_encoded.contiguous()
         Te, B, E = int(dy.shape[0]), int(dy.shape[1]), int(dy.shape[2])
@@ -285,14 +285,14 @@ class Encoder(object):
         genc = self.store.grad[first: first + count]
         acc = ws.get("enc.passes.gacc", (count,))
         dx = None
+        if group is None:
+            group = lib.group()
         for k, (lo, hi) in enumerate(cols):
             child = self._passes[k]
             dk = ws.get(child.pfx + ".dy", (Te, hi - lo, E))
             lib.copy_many([(self._cols2d(dy, lo, hi), dk.view(Te, (hi - lo) * E))])
-            if getattr(lib, "_group", None) is None:
-                lib.begin_group()
-            dxk = child.backward(dk, need_input_grad=need_input_grad)
-            lib.flush_group(ws.get("gemm_ws.grouped", (1 << 26,)))
+            dxk = child.backward(dk, need_input_grad=need_input_grad, group=group)
+            group.flush(ws.get("gemm_ws.grouped", (1 << 26,)))
             child.finish_backward()
             if need_input_grad:
                 if dx is None:
@@ -357,12 +357,14 @@ class Encoder(object):
             self._saved = saved
         return x, m
 
-    def backward(self, d_encoded, need_input_grad=False):
+    def backward(self, d_encoded, need_input_grad=False, group=None):
         """d_encoded (T',B,2H_last): gradient wrt `encoded`.  Writes the encoder parameter gradients; returns the gradient
-        wrt the encoder input when `need_input_grad` (a bottom MLP sits in front), else None."""
+        wrt the encoder input when `need_input_grad` (a bottom MLP sits in front), else None.  With a `group` (native.GemmGroup)
+        the recurrent weight-gradient products and the fork column sums join it: the caller flushes it and then calls
+        finish_backward().  Without one everything launches here."""
         d, p, g, lib, ws = self.d, self.store.p, self.store.g, self.lib, self.ws
         if self._pass_cols is not None:
-            return self._backward_in_passes(self._pass_cols, d_encoded, need_input_grad)
+            return self._backward_in_passes(self._pass_cols, d_encoded, need_input_grad, group)
         assert self._saved is not None, "apply() must run first"
         gemm_ws = ws.get("gemm_ws", (1 << 22,))
         self._scatter = []
@@ -399,48 +401,51 @@ class Encoder(object):
             # weight gradients are off the critical path; with `self.overlap = True` they go to a second stream and overlap the next
             # layer's recurrence (see __init__ for why this is not the default)
             with self._side_stream() as side_ws:
+                wgrad, colsum = lib.weight_grad_calls(group, side_ws)
                 for di, direction in enumerate(("forward", "backward")):
                     n = self._names(i, direction)
                     dc = dxg2[:, di * 3 * H: di * 3 * H + H]
                     dg = dxg2[:, di * 3 * H + H: di * 3 * H + 3 * H]
                     hcol = slice(di * H, (di + 1) * H)
-                    lib.sgemm(rh2[:, hcol], dc, g[n["Whh"]], transA=True, ws=side_ws, group=True)
+                    wgrad(rh2[:, hcol], dc, g[n["Whh"]])
                     if T > 1:
                         if di == 0:     # h_{t-1} = y[t-1]
-                            lib.sgemm(y2[: (T - 1) * B, hcol], dg[B:], g[n["Whg"]], transA=True, ws=side_ws, group=True)
+                            wgrad(y2[: (T - 1) * B, hcol], dg[B:], g[n["Whg"]])
                         else:           # backward direction: previous state in scan order is y[t+1]
-                            lib.sgemm(y2[B:, hcol], dg[: (T - 1) * B], g[n["Whg"]], transA=True, ws=side_ws, group=True)
+                            wgrad(y2[B:, hcol], dg[: (T - 1) * B], g[n["Whg"]])
                         beta = 1.0
                     else:
                         beta = 0.0
-                    # the first scan step starts from the (broadcast) initial state: rank-B update with lda = 0
+                    # the first scan step starts from the (broadcast) initial state: rank-B update with lda = 0, onto the product above
                     first = dg[:B] if di == 0 else dg[(T - 1) * B:]
-                    lib.sgemm(p[n["h0"]], first, g[n["Whg"]], transA=True, beta=beta, M=H, K=B, lda=0, group=True)
+                    if group is not None:
+                        group.add_after(p[n["h0"]], first, g[n["Whg"]], beta=beta, M=H, K=B, lda=0)
+                    else:
+                        lib.sgemm(p[n["h0"]], first, g[n["Whg"]], transA=True, beta=beta, M=H, K=B, lda=0)
                 # fork gradients of both directions: one (I, 6H) product and one column sum, scattered into the four matrices
                 gW = ws.get("enc%d.gWcat" % i, (I, 6 * H))
                 gb = ws.get("enc%d.gbcat" % i, (6 * H,))
                 # (not a member of the grouped launch: with 48 output tiles it fills the chip alone, and the group's one-size k-chunks
                 # would cost it 13 instead of 5 partial copies of its 3 MB output — measured slower)
                 lib.sgemm(x2, dxg2, gW, transA=True, ws=side_ws)
-                lib.colsum(dxg2, gb, ws=side_ws)
+                colsum(dxg2, gb)
                 for di, direction in enumerate(("forward", "backward")):
                     n = self._names(i, direction)
                     o = di * 3 * H
                     self._scatter += [(gW[:, o: o + H], g[n["Wi"]]), (gW[:, o + H: o + 3 * H], g[n["Wg"]]),
                                       (gb[o: o + H], g[n["bi"]]), (gb[o + H: o + 3 * H], g[n["bg"]])]
-                if self.overlap and getattr(lib, "_group", None) is not None:
+                if self.overlap and group is not None:
                     # second-stream probes: the grouped products collected so far (this layer's, and — for the top layer — the
                     # decoder's) run NOW on the side stream, beside the next layer's recurrence, not in one launch at the end
-                    lib.flush_group(ws.get("gemm_ws.grouped.side", (1 << 26,)))
-                    lib.begin_group()
+                    group.flush(ws.get("gemm_ws.grouped.side", (1 << 26,)))
             dy = dx
         self.join_side_stream()
-        if getattr(lib, "_group", None) is None:      # no grouped launch pending: the fork gradients are there
+        if group is None:      # nothing was deferred: the fork gradients are there
             self.finish_backward()
         return dy
 
     def finish_backward(self):
         """Scatter the concatenated fork gradients of all layers into the four parameters each (one launch per 32 pieces).
-        Call after the grouped weight-gradient products have been flushed (the fork products are members of the group)."""
+        backward(group=...) leaves this to its caller: it must follow the group's flush, which runs the fork column sums."""
         self.lib.copy_many(self._scatter)
         self._scatter = []

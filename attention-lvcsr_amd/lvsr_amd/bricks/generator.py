@@ -74,10 +74,11 @@ class SequenceGenerator(object):
         ld = (3 * self.d.D + 3) // 4 * 4
         return self.ws.get("gen.AW", (Tp * B, ld))[:, : 3 * self.d.D], ld
 
-    def _merge_states_backward(self, S2, dR1, gws):
+    def _merge_states_backward(self, S2, dR1, gws, group=None):
         """Gradient of the readout's state source: weight gradient into the store, -> dS_r (rows, state width)."""
         d, p, g, n, lib, ws = self.d, self.store.p, self.store.g, self.n, self.lib, self.ws
-        lib.sgemm(S2, dR1, g[n["Wms"]], transA=True, ws=gws, group=True)
+        wgrad, _ = lib.weight_grad_calls(group, gws)
+        wgrad(S2, dR1, g[n["Wms"]])
         dS_r = ws.get("gen.dS_r", (S2.shape[0], d.D))
         lib.sgemm(dR1, p[n["Wms"]], dS_r, transB=True)
         return dS_r
@@ -369,9 +370,10 @@ class SequenceGenerator(object):
                 st = new
         return out.view(L * B, self.d.V)
 
-    def backward(self):
+    def backward(self, group=None):
         """Gradient of sum(cost_matrix) wrt every generator parameter (written to store.g) and wrt `attended`
-        (returned, (T',B,E))."""
+        (returned, (T',B,E)).  With a `group` (native.GemmGroup) the weight-gradient products and bias column sums join it and
+        are final only after the caller's flush; without one they launch here."""
         d, p, g, n, lib, ws = self.d, self.store.p, self.store.g, self.n, self.lib, self.ws
         sv = self._saved
         assert sv is not None, "cost_matrix() must run first"
@@ -385,12 +387,13 @@ class SequenceGenerator(object):
         bufs, pk = sv["bufs"], sv["pk"]
         nrows = L * B
         gws = ws.get("gemm_ws", (1 << 22,))
+        wgrad, colsum = lib.weight_grad_calls(group, gws)
         S2, WA2 = bufs["S"][:L].view(nrows, self._state_width()), bufs["WA"].view(nrows, d.E)
         dlogits, R1, R2 = sv["dlogits"], sv["R1"], sv["R2"]
         # ---- readout backward
         if d.post_merge:
-            lib.sgemm(R2, dlogits, g[n["Wout"]], transA=True, ws=gws, group=True)
-            lib.colsum(dlogits, g[n["bout"]], ws=gws)
+            wgrad(R2, dlogits, g[n["Wout"]])
+            colsum(dlogits, g[n["bout"]])
             dR2 = ws.get("gen.dR2", (nrows, R2.shape[1]))
             lib.sgemm(dlogits, p[n["Wout"]], dR2, transB=True)
             for j in range(len(self.pm_hidden) - 1, -1, -1):          # the further post-merge layers, last first
@@ -399,40 +402,40 @@ class SequenceGenerator(object):
                 dpre = ws.get("gen.pm_dpre%d" % j, (nrows, width))
                 lib.call("lvsr_act_bwd", lib.stream_for(dpre), ACT_KIND[d.act], lib_ptr(pre), width, lib_ptr(dR2), width, nrows, width,
                          lib_ptr(dpre), width)
-                lib.sgemm(xin, dpre, g[wn], transA=True, ws=gws, group=True)
-                lib.colsum(dpre, g[bn], ws=gws)
+                wgrad(xin, dpre, g[wn])
+                colsum(dpre, g[bn])
                 dR2 = ws.get("gen.pm_dx%d" % j, (nrows, xin.shape[1]))
                 lib.sgemm(dpre, p[wn], dR2, transB=True)
             dR1 = ws.get("gen.dR1", (nrows, d.P))
             lib.call("lvsr_act_bwd", lib.stream_for(dR1), ACT_KIND[d.act], lib_ptr(R1), d.P, lib_ptr(dR2), d.Pout, nrows, d.P,
                      lib_ptr(dR1), d.P)
-            lib.colsum(dR1, g[n["bpm"]], ws=gws)
+            colsum(dR1, g[n["bpm"]])
         else:
             dR1 = dlogits
-            lib.colsum(dR1, g[n["bro"]], ws=gws)
-        lib.sgemm(WA2, dR1, g[n["Wmw"]], transA=True, ws=gws, group=True)
+            colsum(dR1, g[n["bro"]])
+        wgrad(WA2, dR1, g[n["Wmw"]])
         dWA_r = ws.get("gen.dWA_r", (nrows, d.E))
         lib.sgemm(dR1, p[n["Wmw"]], dWA_r, transB=True)
         dS_r = None
         if d.use_states_for_readout:
-            dS_r = self._merge_states_backward(S2, dR1, gws)
-        rb = self._backward_recurrent(sv, dWA_r, dS_r, gws)
+            dS_r = self._merge_states_backward(S2, dR1, gws, group)
+        rb = self._backward_recurrent(sv, dWA_r, dS_r, gws, group)
         accH, accWe, accEb, DCV, dPA, DWA = rb["accH"], rb["accWe"], rb["accEb"], rb["DCV"], rb["dPA"], rb["DWA"]
         import ctypes
         st = lib.stream_for(dPA)
-        lib.colsum(accWe, g[n["we"]].view(-1), ws=gws)
+        colsum(accWe, g[n["we"]].view(-1))
         if d.energy_bias:
-            lib.colsum(accEb, g[n["eb"]], ws=gws)
+            colsum(accEb, g[n["eb"]])
         if d.conv:
-            lib.colsum(accH, g[n["handler"]].view(-1), ws=gws)
+            colsum(accH, g[n["handler"]].view(-1))
             # partial sums per chunk of (label, utterance) rows: at most one chunk per row (large per-GPU batches outgrow gemm_ws)
             fws = ws.get("gen.filter_ws", (max(1 << 20, L * B * d.K * (2 * d.c + 1)),))
             lib.call("lvsr_attdec_filter_grad", st, ctypes.byref(rb["fwd_args"]), lib_ptr(DCV), lib_ptr(g[n["filters"]]), lib_ptr(fws),
                      fws.numel() * 4)
         # ---- attended: preprocess backward + glimpse backward
         A2, dPA2 = sv["A"].view(Tp * B, d.E), dPA.view(Tp * B, d.M)
-        lib.sgemm(A2, dPA2, g[n["Wpre"]], transA=True, ws=gws, group=True)
-        lib.colsum(dPA2, g[n["bpre"]], ws=gws)
+        wgrad(A2, dPA2, g[n["Wpre"]])
+        colsum(dPA2, g[n["bpre"]])
         dA = ws.get("gen.dA", (Tp, B, d.E))
         lib.sgemm(dPA2, p[n["Wpre"]], dA.view(Tp * B, d.E), transB=True)
         W = bufs["W"]
@@ -441,7 +444,7 @@ class SequenceGenerator(object):
                  lib_ptr(DWA), B * d.E, d.E, 1.0, lib_ptr(dA), B * d.E, d.E, B)
         return dA
 
-    def _backward_recurrent(self, sv, dWA_r, dS_r, gws):
+    def _backward_recurrent(self, sv, dWA_r, dS_r, gws, group=None):
         """Reverse walk over the labels and the weight gradients of the transition, the glimpse distribution, the state
         transformer and the feedback fork.  -> dict(accH, accWe, accEb: partial sums of the handler / energy vector / energy
         bias gradients (folded by the caller), DCV, dPA, DWA, fwd_args: the forward argument block of the attention)."""
@@ -454,6 +457,7 @@ class SequenceGenerator(object):
         ntile = (Tp + 63) // 64
         Kc = max(d.K, 1)
         import ctypes
+        wgrad, colsum = lib.weight_grad_calls(group, gws)
         DXG = ws.get("gen.DXG", (nrows, 3 * d.D))
         # The glimpse contraction is reassociated (as in the persistent forward): q = DXG . AW + QR — the kernels need no dwa and do
         # not write DWA; the total gradient wrt the weighted averages is formed after the walk, accumulated onto the readout's share
@@ -501,20 +505,20 @@ class SequenceGenerator(object):
         # ---- weight gradients as batched GEMMs over all steps
         dpc, dg = DXG[:, : d.D], DXG[:, d.D:]
         RH2 = bufs["RH"].view(nrows, d.D)
-        lib.sgemm(RH2, dpc, g[n["Whh"]], transA=True, ws=gws, group=True)
-        lib.sgemm(S2, dg, g[n["Whg"]], transA=True, ws=gws, group=True)
-        lib.sgemm(WA2, dpc, g[n["Wdi"]], transA=True, ws=gws, group=True)
-        lib.sgemm(WA2, dg, g[n["Wdg"]], transA=True, ws=gws, group=True)
-        lib.sgemm(S2, DSW, g[n["Ws"]], transA=True, ws=gws, group=True)
-        lib.colsum(ds, g[n["h0"]], ws=gws)
-        lib.colsum(dpc, g[n["bfi"]], ws=gws)
-        lib.colsum(dg, g[n["bfg"]], ws=gws)
+        wgrad(RH2, dpc, g[n["Whh"]])
+        wgrad(S2, dg, g[n["Whg"]])
+        wgrad(WA2, dpc, g[n["Wdi"]])
+        wgrad(WA2, dg, g[n["Wdg"]])
+        wgrad(S2, DSW, g[n["Ws"]])
+        colsum(ds, g[n["h0"]])
+        colsum(dpc, g[n["bfi"]])
+        colsum(dg, g[n["bfg"]])
         st = lib.stream_for(ds)
         labels_flat = sv["labels"].view(-1)
         if d.embed:
             fb = sv["fb"]
-            lib.sgemm(fb, dpc, g[n["Wfi"]], transA=True, ws=gws, group=True)
-            lib.sgemm(fb, dg, g[n["Wfg"]], transA=True, ws=gws, group=True)
+            wgrad(fb, dpc, g[n["Wfi"]])
+            wgrad(fb, dg, g[n["Wfg"]])
             dfb = ws.get("gen.dfb", (nrows, d.FB))
             lib.sgemm(dpc, p[n["Wfi"]], dfb, transB=True)
             lib.sgemm(dg, p[n["Wfg"]], dfb, transB=True, beta=1.0)

@@ -62,10 +62,11 @@ class StackedSequenceGenerator(SequenceGenerator):
     def _initial_state(self):
         return self._cats()["h0_cat"]
 
-    def _merge_states_backward(self, S2, dR1, gws):
+    def _merge_states_backward(self, S2, dR1, gws, group=None):
         d, g, lib, ws = self.d, self.store.g, self.lib, self.ws
+        wgrad, _ = lib.weight_grad_calls(group, gws)
         for l, n in enumerate(self.nl):
-            lib.sgemm(S2[:, l * d.D:(l + 1) * d.D], dR1, g[n["Wms"]], transA=True, ws=gws, group=True)
+            wgrad(S2[:, l * d.D:(l + 1) * d.D], dR1, g[n["Wms"]])
         dS_r = ws.get("gen.dS_r", (S2.shape[0], d.D_tot))
         lib.sgemm(dR1, self._merge_states_weight(), dS_r, transB=True)
         return dS_r
@@ -279,8 +280,9 @@ class StackedSequenceGenerator(SequenceGenerator):
         lib.copy_many([(att_bufs["WA"].view(L * B, E), WA1[:, :E]), (att_bufs["S"][1:].reshape(L * B, d.D_tot)[:, :D], WA1[:, E:])])
         return dict(fields=f, AW0=AW0, AW1=AW1, wd0=wd0, wd1=wd1)
 
-    def _backward_recurrent(self, sv, dWA_r, dS_r, gws):
+    def _backward_recurrent(self, sv, dWA_r, dS_r, gws, group=None):
         d, p, g, lib, ws = self.d, self.store.p, self.store.g, self.lib, self.ws
+        wgrad, colsum = lib.weight_grad_calls(group, gws)
         L, B, Tp, pk, blk = sv["L"], sv["B"], sv["Tp"], sv["pk"], sv["blk"]
         D, E, DT, nrows = d.D, d.E, d.D_tot, sv["L"] * sv["B"]
         att, layers = blk["att"], blk["layers"]
@@ -365,21 +367,21 @@ class StackedSequenceGenerator(SequenceGenerator):
         for l, (n, lay, bwl) in enumerate(zip(self.nl, layers, bws)):
             dpc, dg = bwl["DXG"][:, :D], bwl["DXG"][:, D:]
             lb = lay["bufs"]
-            lib.sgemm(lb["RH"].view(nrows, D), dpc, g[n["Whh"]], transA=True, ws=gws, group=True)
-            lib.sgemm(Scat2[:, l * D:(l + 1) * D], dg, g[n["Whg"]], transA=True, ws=gws, group=True)
+            wgrad(lb["RH"].view(nrows, D), dpc, g[n["Whh"]])
+            wgrad(Scat2[:, l * D:(l + 1) * D], dg, g[n["Whg"]])
             WA2 = lb["WA"].view(nrows, self._E(l))
-            lib.sgemm(WA2[:, :E], dpc, g[n["Wdi"]], transA=True, ws=gws, group=True)
-            lib.sgemm(WA2[:, :E], dg, g[n["Wdg"]], transA=True, ws=gws, group=True)
+            wgrad(WA2[:, :E], dpc, g[n["Wdi"]])
+            wgrad(WA2[:, :E], dg, g[n["Wdg"]])
             if l > 0:
-                lib.sgemm(WA2[:, E:], dpc, g[n["Fi"]], transA=True, ws=gws, group=True)
-                lib.sgemm(WA2[:, E:], dg, g[n["Fg"]], transA=True, ws=gws, group=True)
-            lib.sgemm(Scat2[:, l * D:(l + 1) * D], DSW, g[n["Ws"]], transA=True, ws=gws, group=True)
-            lib.colsum(bwl["ds"], g[n["h0"]], ws=gws)
-            lib.colsum(dpc, g[n["bfi"]], ws=gws)
-            lib.colsum(dg, g[n["bfg"]], ws=gws)
+                wgrad(WA2[:, E:], dpc, g[n["Fi"]])
+                wgrad(WA2[:, E:], dg, g[n["Fg"]])
+            wgrad(Scat2[:, l * D:(l + 1) * D], DSW, g[n["Ws"]])
+            colsum(bwl["ds"], g[n["h0"]])
+            colsum(dpc, g[n["bfi"]])
+            colsum(dg, g[n["bfg"]])
             if d.embed:
-                lib.sgemm(fb, dpc, g[n["Wfi"]], transA=True, ws=gws, group=True)
-                lib.sgemm(fb, dg, g[n["Wfg"]], transA=True, ws=gws, group=True)
+                wgrad(fb, dpc, g[n["Wfi"]])
+                wgrad(fb, dg, g[n["Wfg"]])
                 lib.sgemm(dpc, p[n["Wfi"]], dfb, transB=True, beta=0.0 if l == 0 else 1.0)
                 lib.sgemm(dg, p[n["Wfg"]], dfb, transB=True, beta=1.0)
             else:

@@ -213,28 +213,29 @@ class SpeechRecognizer(object):
     def backward(self):
         """Gradient of cost.sum() wrt all parameters -> self.store.grad (flat) / self.store.g (named views)."""
         with self._on_stream():
-            # the small weight-gradient products of decoder and encoder (recurrent matrices, readout, ...) are collected and
-            # run as ONE grouped launch at the end: alone none of them fills the chip
-            self.lib.begin_group()
-            d_encoded = self.generator.backward()
-            self._backward_encoder(d_encoded)
+            # the small weight-gradient products of decoder and encoder (recurrent matrices, readout, ...) are collected in one
+            # group and run as ONE grouped launch at the end: alone none of them fills the chip
+            group = self.lib.group()
+            d_encoded = self.generator.backward(group)
+            self._backward_encoder(d_encoded, group)
 
     def _backward_decoder(self):
         """The decoder's half of backward() with a grouped launch of its own: afterwards every gradient under
         /recognizer/generator is final (the tail of the flat gradient buffer, `decoder_bucket()`).  -> d_encoded."""
         with self._on_stream():
-            self.lib.begin_group()
-            d_encoded = self.generator.backward()
-            self.lib.flush_group(self.ws.get("gemm_ws.grouped", (1 << 26,)))
+            group = self.lib.group()
+            d_encoded = self.generator.backward(group)
+            group.flush(self.ws.get("gemm_ws.grouped", (1 << 26,)))
             return d_encoded
 
-    def _backward_encoder(self, d_encoded):
-        """Encoder (and bottom) half of backward(); flushes the pending grouped launch (opens one if none is pending)."""
+    def _backward_encoder(self, d_encoded, group=None):
+        """Encoder (and bottom) half of backward(): adds the encoder's products to `group` (the decoder's, from backward(); a fresh
+        one otherwise) and flushes it."""
         with self._on_stream():
-            if getattr(self.lib, "_group", None) is None:
-                self.lib.begin_group()
-            d_bottom = self.encoder.backward(d_encoded, need_input_grad=bool(self.d.bottom_dims))
-            self.lib.flush_group(self.ws.get("gemm_ws.grouped", (1 << 26,)))
+            if group is None:
+                group = self.lib.group()
+            d_bottom = self.encoder.backward(d_encoded, need_input_grad=bool(self.d.bottom_dims), group=group)
+            group.flush(self.ws.get("gemm_ws.grouped", (1 << 26,)))
             self.encoder.finish_backward()
             if self.d.bottom_dims:
                 self.bottom.backward(d_bottom)

@@ -9,6 +9,7 @@ The library is mandatory: if `liblvsr_hip.so` is missing or a call fails this ra
 PyTorch/CPU fallback anywhere in the product path.
 """
 import ctypes
+import functools
 import os
 import re
 
@@ -213,60 +214,21 @@ class Lib(object):
 
     # ---- thin typed wrappers -----------------------------------------------------------------
     # ---- grouped weight-gradient products ---------------------------------------------------------
-    def begin_group(self):
-        """Until flush_group(): sgemm(..., transA=True, group=True) calls are collected instead of launched."""
-        self._group, self._group_after = [], []
-        self._group_colsums = []
+    def group(self):
+        """A fresh GemmGroup: the collector of a backward pass's small weight-gradient products and bias-gradient column sums."""
+        return GemmGroup(self)
 
-    def flush_group(self, ws):
-        """One lvsr_sgemm_tn_grouped launch for everything collected since begin_group() (then the deferred follow-ups, in
-        order).  The operands must still hold what they held when the products were requested."""
-        jobs, after = getattr(self, "_group", None), getattr(self, "_group_after", None)
-        self._group = self._group_after = None
-        if jobs:
-            cls = self.structs["lvsr_gemm_desc"]
-            arr = (cls * len(jobs))()
-            for d, (A, B, C, beta) in zip(arr, jobs):
-                d.A, d.B, d.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
-                d.M, d.N, d.K = A.shape[1], B.shape[1], A.shape[0]
-                d.lda, d.ldb, d.ldc, d.beta = A.stride(0), B.stride(0), C.stride(0), beta
-            self.call("lvsr_sgemm_tn_grouped", self.stream_for(jobs[0][2]), arr, len(jobs), ptr(ws), ws.numel() * 4)
-        after = list(after or ())
-        # the follow-ups (rank-B updates with beta = 1 onto outputs of the grouped launch: K = batch rows, eight of them per step at 9.6 us
-        # a launch) go out as ONE more grouped launch when they are plain transposed-A products onto distinct outputs (round 6)
-        plain = [kw for kw in after if kw["transA"] and not kw["transB"] and kw["alpha"] == 1.0 and kw["bias"] is None
-                 and kw["A"].stride(-1) == 1 and kw["B"].stride(-1) == 1 and kw["C"].stride(-1) == 1]
-        if len(plain) == len(after) and len(after) > 1 and len({kw["C"].data_ptr() for kw in after}) == len(after):
-            cls = self.structs["lvsr_gemm_desc"]
-            arr = (cls * len(after))()
-            for d, kw in zip(arr, after):
-                A, B, C = kw["A"], kw["B"], kw["C"]
-                d.A, d.B, d.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
-                d.M = kw["M"] if kw["M"] is not None else A.shape[1]
-                d.K = kw["K"] if kw["K"] is not None else A.shape[0]
-                d.N = kw["N"] if kw["N"] is not None else B.shape[1]
-                d.lda = kw["lda"] if kw["lda"] is not None else A.stride(0)
-                d.ldb = kw["ldb"] if kw["ldb"] is not None else B.stride(0)
-                d.ldc = kw["ldc"] if kw["ldc"] is not None else C.stride(0)
-                d.beta = float(kw["beta"])
-            self.call("lvsr_sgemm_tn_grouped", self.stream_for(after[0]["C"]), arr, len(after), None, 0)
-        else:
-            for kw in after:
-                self.sgemm(**kw)
-        self._flush_colsums(ws)
+    def weight_grad_calls(self, group, ws):
+        """-> (product, colsum) for the weight gradients of a backward pass: product(A, B, C) is C = A^T @ B, colsum(X, out) a bias
+        gradient.  With a `group` they become its members (launched by whoever flushes it); with None they launch at once, with the
+        split workspace `ws`."""
+        if group is None:
+            return functools.partial(self.sgemm, transA=True, ws=ws), functools.partial(self.colsum, ws=ws)
+        return group.add, functools.partial(group.colsum, ws=ws)
 
     def sgemm(self, A, B, C, transA=False, transB=False, alpha=1.0, beta=0.0, bias=None, ws=None,
-              M=None, N=None, K=None, lda=None, ldb=None, ldc=None, group=False):
-        """C = alpha*op(A)@op(B) + beta*C + bias.  A,B,C are 2-D (possibly strided-row) fp32 tensors.
-        group=True (weight gradients, transA only): join the pending grouped launch if one is open (begin_group)."""
-        if group and getattr(self, "_group", None) is not None:
-            plain = transA and not transB and alpha == 1.0 and bias is None and M is None and K is None and lda is None
-            if plain and A.stride(1) == 1 and B.stride(1) == 1 and C.stride(1) == 1:
-                self._group.append((A, B, C, float(beta)))
-            else:       # depends on a collected product (e.g. a rank-B update with beta = 1): after the grouped launch, in order
-                self._group_after.append(dict(A=A, B=B, C=C, transA=transA, transB=transB, alpha=alpha, beta=beta, bias=bias, ws=ws,
-                                              M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc))
-            return
+              M=None, N=None, K=None, lda=None, ldb=None, ldc=None):
+        """C = alpha*op(A)@op(B) + beta*C + bias.  A,B,C are 2-D (possibly strided-row) fp32 tensors."""
         if M is None:
             M = A.shape[1] if transA else A.shape[0]
         if K is None:
@@ -280,35 +242,12 @@ class Lib(object):
                   beta, ptr(C), ldc, ptr(bias), ptr(ws), (ws.numel() * 4 if ws is not None else 0))
 
     def colsum(self, X, out, beta=0.0, M=None, N=None, ldx=None, ws=None):
-        """out[n] = beta * out[n] + sum_m X[m, n].  While a grouped launch is open (begin_group) the sum is collected and runs with the
-        others in ONE lvsr_colsum_many launch at flush_group() — X must still hold its values then, `out` must not be read before
-        (the bias gradients of a backward pass: 21 launches of 5-13 us per training step before round 6)."""
+        """out[n] = beta * out[n] + sum_m X[m, n]."""
         M = X.shape[0] if M is None else M
         N = X.shape[1] if N is None else N
         ldx = X.stride(0) if ldx is None else ldx
-        pending = getattr(self, "_group_colsums", None)
-        if pending is not None and getattr(self, "_group", None) is not None:
-            pending.append((X, out, float(beta), int(M), int(N), int(ldx), (ws.numel() * 4 if ws is not None else 0)))
-            return
         self.call("lvsr_colsum", self.stream_for(out), ptr(X), M, N, ldx, ptr(out), beta,
                   ptr(ws), (ws.numel() * 4 if ws is not None else 0))
-
-    def _flush_colsums(self, ws):
-        pending, self._group_colsums = getattr(self, "_group_colsums", None), None
-        if not pending:
-            return
-        outs = {p[1].data_ptr() for p in pending}
-        split_ws = {p[6] for p in pending}
-        if len(outs) != len(pending) or len(split_ws) != 1 or len(pending) > 32:
-            for X, out, beta, M, N, ldx, wsb in pending:       # (a shared output or mixed workspaces: as separate launches, in order)
-                self.call("lvsr_colsum", self.stream_for(out), ptr(X), M, N, ldx, ptr(out), beta, ptr(ws) if wsb else None, min(wsb, ws.numel() * 4))
-            return
-        cls = self.structs["lvsr_colsum_desc"]
-        arr = (cls * len(pending))()
-        for d, (X, out, beta, M, N, ldx, wsb) in zip(arr, pending):
-            d.X, d.out, d.M, d.N, d.ldx, d.beta = X.data_ptr(), out.data_ptr(), M, N, ldx, beta
-        wsb = split_ws.pop()
-        self.call("lvsr_colsum_many", self.stream_for(pending[0][1]), arr, len(pending), ptr(ws) if wsb else None, ws.numel() * 4 if wsb else 0, wsb)
 
     def copy_many(self, pairs):
         """pairs: [(src, dst)] or [(src, dst, beta)] of equally shaped 1-D / 2-D fp32 tensors with unit inner stride -> one
@@ -385,6 +324,85 @@ class Lib(object):
     def unique_token(cls):
         cls._uid[0] += 1
         return cls._uid[0]
+
+
+class GemmGroup(object):
+    """The small transposed-A weight-gradient products and the bias-gradient column sums of a backward pass, collected to go out as a
+    few grouped launches (alone none of them fills the chip; the column sums were 21 launches of 5-13 us per training step).  Whoever
+    makes the group (`lib.group()`) passes it down and flushes it; dropping it unflushed launches nothing.  The operands must still
+    hold their values at `flush()`, and no output may be read before."""
+    def __init__(self, lib):
+        self.lib = lib
+        self.first, self.after, self.colsums = [], [], []
+
+    @staticmethod
+    def _member(A, B, C, beta, M=None, N=None, K=None, lda=None, ldb=None, ldc=None):
+        assert A.stride(-1) == 1 and B.stride(-1) == 1 and C.stride(-1) == 1, "grouped products need unit inner strides"
+        dims = (A.shape[1] if M is None else M, B.shape[1] if N is None else N, A.shape[0] if K is None else K,
+                A.stride(0) if lda is None else lda, B.stride(0) if ldb is None else ldb, C.stride(0) if ldc is None else ldc)
+        return (A, B, C, float(beta)) + tuple(int(v) for v in dims)
+
+    def add(self, A, B, C, beta=0.0):
+        """First-wave member: C = A^T @ B + beta * C over whole 2-D tensors."""
+        assert A.dim() == B.dim() == C.dim() == 2
+        self.first.append(self._member(A, B, C, beta))
+
+    def add_after(self, A, B, C, beta=0.0, **sizes):
+        """Follow-up: the same product, optionally with explicit `sizes` (M, N, K, lda, ldb, ldc as in Lib.sgemm), run after the
+        first wave — e.g. a rank-B update with beta = 1 onto a first-wave output."""
+        self.after.append(self._member(A, B, C, beta, **sizes))
+
+    def colsum(self, X, out, beta=0.0, M=None, N=None, ldx=None, ws=None):
+        """Deferred Lib.colsum; of `ws` only the size counts (0: the sum must not split its rows), flush() brings the memory."""
+        self.colsums.append((X, out, float(beta), int(X.shape[0] if M is None else M), int(X.shape[1] if N is None else N),
+                             int(X.stride(0) if ldx is None else ldx), (ws.numel() * 4 if ws is not None else 0)))
+
+    @staticmethod
+    def _independent(members):
+        """No member reads or writes storage that another member writes (they may then share one concurrent launch)."""
+        def span(t, rows, cols, ld):
+            return t.data_ptr(), t.data_ptr() + 4 * ((rows - 1) * ld + cols if rows > 0 and cols > 0 else 0)
+        spans = [(span(A, K, M, lda), span(B, K, N, ldb), span(C, M, N, ldc)) for A, B, C, _, M, N, K, lda, ldb, ldc in members]
+        return not any(lo < c_hi and c_lo < hi
+                       for i, mine in enumerate(spans) for j, (_, _, (c_lo, c_hi)) in enumerate(spans) if i != j
+                       for lo, hi in mine)
+
+    def _launch_grouped(self, members, ws):
+        arr = (self.lib.structs["lvsr_gemm_desc"] * len(members))()
+        for d, (A, B, C, beta, M, N, K, lda, ldb, ldc) in zip(arr, members):
+            d.A, d.B, d.C = A.data_ptr(), B.data_ptr(), C.data_ptr()
+            d.M, d.N, d.K, d.lda, d.ldb, d.ldc, d.beta = M, N, K, lda, ldb, ldc, beta
+        self.lib.call("lvsr_sgemm_tn_grouped", self.lib.stream_for(members[0][2]), arr, len(members), ptr(ws),
+                      ws.numel() * 4 if ws is not None else 0)
+
+    def flush(self, ws):
+        """Launch what was collected and leave the group empty: the first wave as one lvsr_sgemm_tn_grouped (split workspace `ws`);
+        the follow-ups as one more grouped launch when there are several and they are independent, else one lvsr_sgemm each, in order;
+        the column sums as one lvsr_colsum_many (one lvsr_colsum each, in order, when they share an output, mix workspaces or are
+        more than 32)."""
+        lib = self.lib
+        first, after, colsums = self.first, self.after, self.colsums
+        self.first, self.after, self.colsums = [], [], []
+        if first:
+            self._launch_grouped(first, ws)
+        # (the encoder's rank-B updates: K = batch rows, eight of them per step at 9.6 us a launch)
+        if len(after) > 1 and self._independent(after):
+            self._launch_grouped(after, None)
+        else:
+            for A, B, C, beta, M, N, K, lda, ldb, ldc in after:
+                lib.sgemm(A, B, C, transA=True, beta=beta, M=M, N=N, K=K, lda=lda, ldb=ldb, ldc=ldc)
+        if not colsums:
+            return
+        split_ws = {c[6] for c in colsums}
+        if len({c[1].data_ptr() for c in colsums}) != len(colsums) or len(split_ws) != 1 or len(colsums) > 32:
+            for X, out, beta, M, N, ldx, wsb in colsums:
+                lib.call("lvsr_colsum", lib.stream_for(out), ptr(X), M, N, ldx, ptr(out), beta, ptr(ws) if wsb else None, min(wsb, ws.numel() * 4))
+            return
+        arr = (lib.structs["lvsr_colsum_desc"] * len(colsums))()
+        for d, (X, out, beta, M, N, ldx, wsb) in zip(arr, colsums):
+            d.X, d.out, d.M, d.N, d.ldx, d.beta = X.data_ptr(), out.data_ptr(), M, N, ldx, beta
+        wsb = split_ws.pop()
+        lib.call("lvsr_colsum_many", lib.stream_for(colsums[0][1]), arr, len(colsums), ptr(ws) if wsb else None, ws.numel() * 4 if wsb else 0, wsb)
 
 
 class Region(object):

@@ -264,6 +264,18 @@ def test_colsum_many_gpu(gpu_device):
     run_colsum_many(gpu_device, native.get())
 
 
+def test_grouped_products_gpu(gpu_device):
+    from test_emu_gemm import run_grouped_products
+    from lvsr_amd import native
+    run_grouped_products(gpu_device, native.get())
+
+
+def test_grouped_followups_gpu(gpu_device):
+    from test_emu_gemm import run_grouped_followups
+    from lvsr_amd import native
+    run_grouped_followups(gpu_device, native.get())
+
+
 def test_gemm_tile_shape_independence_gpu(gpu_device):
     from test_emu_gemm import run_tile_shape_independence
     from lvsr_amd import native
