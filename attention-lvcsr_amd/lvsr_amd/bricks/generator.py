@@ -14,10 +14,13 @@ import os
 import numpy
 import torch
 
+from ..native import ptr
+
 ACT_KIND = {"identity": 0, "maxout2": 1, "rectifier": 2, "tanh": 3}
 NORMALIZER_KIND = {"softmax": 0, "logistic": 1, "relu": 2}
 PRIOR_KIND = {"expanding": 0, "window_around_mean": 1, "window_around_median": 2}
 ATT_MS = 32     # match-dim slice per work-group in the energy kernels (csrc/decoder.h)
+CTL = dict(nlive=0, pos=1, done=2, nfin=3, patience=4, nsel=5, err=6, steps=7)      # words of a beam search's control block (csrc/beam.hip)
 
 
 def _f32(x):
@@ -25,6 +28,8 @@ def _f32(x):
 
 
 class SequenceGenerator(object):
+    language_model = None
+
     def __init__(self, dims, store, lib, workspace, use_graph=True, use_persistent=None):
         self.d = dims
         self.store = store
@@ -35,7 +40,6 @@ class SequenceGenerator(object):
         self.use_persistent_bwd = None            # None: follows use_persistent; False: step kernels for the reverse walk only (probes)
         self._packs = None
         self._pack_cache = {}
-        self._gen_cache = {}
         self._saved = None
         g = "/recognizer/generator"
         att = g + "/att_trans/" + ("conv_att" if dims.conv else "cont_att")
@@ -150,42 +154,105 @@ class SequenceGenerator(object):
             return 0, (float(pr["initial_begin"]), float(pr["initial_end"]), _f32(pr["min_speed"]), _f32(pr["max_speed"]))
         return kind, (float(pr["before"]), float(pr["after"]), 0.0, 0.0)
 
-    # ---- argument block shared by training and generation ------------------------------------------
-    def _attdec_fields(self, pk, A, PA, Am, L, B, bufs, phases, step0, broadcast, groups=0, group_Tp=None):
-        d, p, n = self.d, self.store.p, self.n
-        Tp = int(A.shape[0])
-        kind, pp = self._prior()
+    def _pos_needed(self):
+        """Do the rows carry window centres (slot `pos`)?  The windowed priors of a location-aware attention only."""
+        return bool(self.d.conv and self._prior()[0] != 0)
+
+    # ---- slots and argument block shared by training and generation -----------------------------------
+    def _attdec_bufs(self, prefix, suffix, steps, rows, Tp=None, att=True, gru=True, ZB=False, **given):
+        """The slots of `lvsr_attdec_args` for `steps` label steps of `rows` rows: workspace buffers `prefix + slot + suffix`.
+        att: the attention part (S, W, pos, WA, EN, sW, CV, ep; ZB = with the normaliser sums the backward pass reads);
+        gru: the GRU part (U, R, C, RH, sg, xin).  `given`: slots the caller holds already — xg and ymask, state slots it
+        has initialised, a stack layer's column block of S and its distribution input WA; they are not requested."""
+        d, ws = self.d, self.ws
+        D, Kc = d.D, max(d.K, 1)
+
+        def get(slot, *shape):
+            return given[slot] if slot in given else ws.get(prefix + slot + suffix, shape)
+        b = dict(given)
+        if att:
+            b.update(S=get("S", steps + 1, rows, self._state_width()), W=get("W", steps + 1, rows, Tp),
+                     pos=get("pos", steps + 1, rows) if self._pos_needed() else None,
+                     WA=get("WA", steps, rows, d.E), EN=get("EN", steps, rows, Tp), ZB=get("ZB", steps, rows) if ZB else None,
+                     sW=get("sW", steps, rows, d.M), CV=get("CV", steps, rows, Kc, Tp) if d.conv else None)
+        if gru:
+            b.update(U=get("U", steps, rows, D), R=get("R", steps, rows, D), C=get("C", steps, rows, D), RH=get("RH", steps, rows, D),
+                     sg=get("sg", rows, 2 * D), xin=get("xin", rows, D))
+        if att:
+            b["ep"] = get("ep", rows, (d.M + ATT_MS - 1) // ATT_MS, Tp)
+        return b
+
+    def _strides(self, B, broadcast, groups=0, group_Tp=None):
+        """How row b of a block finds its utterance in A / PA / Am."""
+        d = self.d
         if groups:         # batched beam search: rows [g B/groups, (g+1) B/groups) read utterance g (lvsr_attdec_args.group_rows)
-            strides = dict(A_ts=groups * d.E, A_bs=d.E, PA_ts=groups * d.M, PA_bs=d.M, Am_ts=groups, Am_bs=1,
-                           group_rows=B // groups, step_stride=16, group_Tp=group_Tp)
-        elif broadcast:    # one utterance shared by every hypothesis (beam search)
-            strides = dict(A_ts=d.E, A_bs=0, PA_ts=d.M, PA_bs=0, Am_ts=1, Am_bs=0)
-        else:
-            strides = dict(A_ts=B * d.E, A_bs=d.E, PA_ts=B * d.M, PA_bs=d.M, Am_ts=B, Am_bs=1)
-        f = dict(Tp=Tp, B=B, L=L, E=d.E, D=d.D, M=d.M, K=d.K, c=d.c, prior_type=kind, step0=step0, phases=phases,
-                 p0=pp[0], p1=pp[1], p2=pp[2], p3=pp[3], A=A, PA=PA, Am=Am, Ws_p=pk["Ws"], w_e=p[n["we"]],
+            return dict(A_ts=groups * d.E, A_bs=d.E, PA_ts=groups * d.M, PA_bs=d.M, Am_ts=groups, Am_bs=1,
+                        group_rows=B // groups, step_stride=16, group_Tp=group_Tp)
+        if broadcast:      # one utterance shared by every hypothesis (beam search)
+            return dict(A_ts=d.E, A_bs=0, PA_ts=d.M, PA_bs=0, Am_ts=1, Am_bs=0)
+        return dict(A_ts=B * d.E, A_bs=d.E, PA_ts=B * d.M, PA_bs=d.M, Am_ts=B, Am_bs=1)
+
+    def _att_fields(self, A, PA, Am, L, B, D, bufs, phases, step0, broadcast, groups=0, group_Tp=None):
+        """The attention half of the argument block over states of width D: sizes, prior, normaliser, the energy parameters, the
+        contexts with their strides, and the slots.  The weights of the state transformer are the caller's (packed or plain)."""
+        d, p, n = self.d, self.store.p, self.n
+        kind, pp = self._prior()
+        f = dict(Tp=int(A.shape[0]), B=B, L=L, E=d.E, D=D, M=d.M, K=d.K, c=d.c, prior_type=kind, step0=step0, phases=phases,
+                 p0=pp[0], p1=pp[1], p2=pp[2], p3=pp[3], A=A, PA=PA, Am=Am, w_e=p[n["we"]],
                  normalizer=NORMALIZER_KIND[d.normalizer], e_bias=p[n["eb"]] if d.energy_bias else None,
-                 filters=p[n["filters"]] if d.conv else None, handler=p[n["handler"]] if d.conv else None,
-                 Whg_p=pk["Whg"], Whh_p=pk["Whh"], Wdi_p=pk["Wdi"], Wdg_p=pk["Wdg"])
-        f.update(strides)
+                 filters=p[n["filters"]] if d.conv else None, handler=p[n["handler"]] if d.conv else None)
+        f.update(self._strides(B, broadcast, groups, group_Tp))
         f.update(bufs)
         return f
 
-    def _feedback_fork(self, labels_flat, nrows, xg, fb_buf=None):
-        """xg (nrows,3D) = fork(feedback(labels)): LookupFeedback / OneOfNFeedback then Fork of two Linear bricks
-        (sequence_generators.py:263-264, 839-842; lvsr/bricks/__init__.py:97-104)."""
-        d, p, n, lib = self.d, self.store.p, self.n, self.lib
-        st = lib.stream_for(xg)
+    def _gru_fields(self, pk, l=""):
+        """The packed weights of a GRU block (layer l of a stack)."""
+        return dict(Whg_p=pk["Whg%s" % l], Whh_p=pk["Whh%s" % l], Wdi_p=pk["Wdi%s" % l], Wdg_p=pk["Wdg%s" % l])
+
+    def _attdec_fields(self, pk, A, PA, Am, L, B, bufs, phases, step0, broadcast, groups=0, group_Tp=None):
+        f = self._att_fields(A, PA, Am, L, B, self.d.D, bufs, phases, step0, broadcast, groups, group_Tp)
+        f.update(self._gru_fields(pk), Ws_p=pk["Ws"])
+        return f
+
+    def _feedback_forks(self, labels_flat, nrows, layers, fb_buf=None):
+        """xg (nrows,3D) = fork(feedback(labels)) for every (parameter names, xg) of `layers`: LookupFeedback / OneOfNFeedback
+        then Fork of two Linear bricks (sequence_generators.py:263-264, 839-842; lvsr/bricks/__init__.py:97-104); one pair
+        here, one per layer of a stack (fork_inputs#l)."""
+        d, p, lib = self.d, self.store.p, self.lib
+        st = lib.stream_for(layers[0][1])
         if d.embed:
-            lib.call("lvsr_gather_rows", st, lib_ptr(p[n["table"]]), d.FB, lib_ptr(labels_flat), nrows, d.V + 1, d.FB,
-                     None, lib_ptr(fb_buf), d.FB)
-            lib.sgemm(fb_buf, p[n["Wfi"]], xg[:, : d.D], bias=p[n["bfi"]])
-            lib.sgemm(fb_buf, p[n["Wfg"]], xg[:, d.D:], bias=p[n["bfg"]])
+            lib.call("lvsr_gather_rows", st, ptr(p[self.n["table"]]), d.FB, ptr(labels_flat), nrows, d.V + 1, d.FB,
+                     None, ptr(fb_buf), d.FB)
+        for n, xg in layers:
+            if d.embed:
+                lib.sgemm(fb_buf, p[n["Wfi"]], xg[:, : d.D], bias=p[n["bfi"]])
+                lib.sgemm(fb_buf, p[n["Wfg"]], xg[:, d.D:], bias=p[n["bfg"]])
+            else:
+                lib.call("lvsr_gather_rows", st, ptr(p[n["Wfi"]]), d.D, ptr(labels_flat), nrows, d.FB, d.D,
+                         ptr(p[n["bfi"]]), ptr(xg), 3 * d.D)
+                lib.call("lvsr_gather_rows", st, ptr(p[n["Wfg"]]), 2 * d.D, ptr(labels_flat), nrows, d.FB, 2 * d.D,
+                         ptr(p[n["bfg"]]), ptr(xg[:, d.D:]), 3 * d.D)
+
+    def _feedback_forks_backward(self, l, n, sv, DXG, dfb, wgrad):
+        """Layer l's share of the backward pass of `_feedback_forks` (n = its parameter names, DXG (rows,3D) the gradient of its
+        xg): the fork's weight gradients; with lookup feedback the gradient of the embedded labels `dfb` adds up over the layers
+        and goes to the table after the last."""
+        d, p, g, lib = self.d, self.store.p, self.store.g, self.lib
+        dpc, dg = DXG[:, : d.D], DXG[:, d.D:]
+        nrows, st, labels_flat = int(DXG.shape[0]), lib.stream_for(DXG), sv["labels"].view(-1)
+        if d.embed:
+            wgrad(sv["fb"], dpc, g[n["Wfi"]])
+            wgrad(sv["fb"], dg, g[n["Wfg"]])
+            lib.sgemm(dpc, p[n["Wfi"]], dfb, transB=True, beta=0.0 if l == 0 else 1.0)
+            lib.sgemm(dg, p[n["Wfg"]], dfb, transB=True, beta=1.0)
+            if l == d.n_dec - 1:
+                lib.call("lvsr_scatter_add_rows", st, ptr(dfb), d.FB, ptr(labels_flat), nrows, d.V + 1, d.FB,
+                         ptr(g[self.n["table"]]), d.FB, 0.0)
         else:
-            lib.call("lvsr_gather_rows", st, lib_ptr(p[n["Wfi"]]), d.D, lib_ptr(labels_flat), nrows, d.FB, d.D,
-                     lib_ptr(p[n["bfi"]]), lib_ptr(xg), 3 * d.D)
-            lib.call("lvsr_gather_rows", st, lib_ptr(p[n["Wfg"]]), 2 * d.D, lib_ptr(labels_flat), nrows, d.FB, 2 * d.D,
-                     lib_ptr(p[n["bfg"]]), lib_ptr(xg[:, d.D:]), 3 * d.D)
+            lib.call("lvsr_scatter_add_rows", st, ptr(dpc), 3 * d.D, ptr(labels_flat), nrows, d.FB, d.D,
+                     ptr(g[n["Wfi"]]), d.D, 0.0)
+            lib.call("lvsr_scatter_add_rows", st, ptr(dg), 3 * d.D, ptr(labels_flat), nrows, d.FB, 2 * d.D,
+                     ptr(g[n["Wfg"]]), 2 * d.D, 0.0)
 
     def preprocess(self, attended):
         """attention.preprocess (lvsr/bricks/attention.py:228-230): PA = attended @ W + b."""
@@ -207,12 +274,12 @@ class SequenceGenerator(object):
         if not d.post_merge:
             return R1, None, R1
         R2 = ws.get("gen.R2" + tag, (nrows, d.Pout))
-        lib.call("lvsr_act_fwd", lib.stream_for(R2), ACT_KIND[d.act], lib_ptr(R1), d.P, nrows, d.P, lib_ptr(R2), d.Pout)
+        lib.call("lvsr_act_fwd", lib.stream_for(R2), ACT_KIND[d.act], ptr(R1), d.P, nrows, d.P, ptr(R2), d.Pout)
         for j, (wn, bn, width) in enumerate(self.pm_hidden):
             pre = ws.get("gen.pm_pre%d" % j + tag, (nrows, width))
             lib.sgemm(R2, p[wn], pre, bias=p[bn])
             post = ws.get("gen.pm_post%d" % j + tag, (nrows, width))
-            lib.call("lvsr_act_fwd", lib.stream_for(post), ACT_KIND[d.act], lib_ptr(pre), width, nrows, width, lib_ptr(post), width)
+            lib.call("lvsr_act_fwd", lib.stream_for(post), ACT_KIND[d.act], ptr(pre), width, nrows, width, ptr(post), width)
             self._pm_acts.append((R2, pre))
             R2 = post
         logits = ws.get("gen.logits" + tag, (nrows, d.V))
@@ -220,38 +287,55 @@ class SequenceGenerator(object):
         return R1, R2, logits
 
     # ---- persistent label loop -------------------------------------------------------------------
-    def _persistent_ws(self, fields):
-        """Workspace of the persistent decoder kernel for this argument block, or None when the step kernels run: the
-        configuration is outside the kernel's limits (lvsr_attdec_persist_ws_bytes == 0), `use_persistent=False`, or — on the
-        CPU emulator — its work-groups are not run concurrently."""
-        mode = "auto" if self.use_persistent is None else ("1" if self.use_persistent else "0")
-        if mode == "0":
-            return None
-        import ctypes as _ct
-        a = self.lib.make("lvsr_attdec_args", **fields)
-        nbytes = int(self.lib._lvsr_attdec_persist_ws_bytes(_ct.byref(a)))
-        if self.lib.is_emulator and not self.lib.emulates_concurrency():
+    def _persist_sync(self, query, args, name, emulated=True):
+        """The int32 workspace `name` of a persistent kernel, of the size the library's `query` gives for the argument block, or
+        None when the kernel does not apply: the configuration is outside its limits (0 bytes) or — `emulated`, on the CPU
+        emulator — work-groups are not run concurrently."""
+        nbytes = int(getattr(self.lib, "_" + query)(ctypes.byref(args)))
+        if emulated and self.lib.is_emulator and not self.lib.emulates_concurrency():
             nbytes = 0
-        if nbytes == 0:
-            if mode == "1":
-                raise ValueError("persistent decoder kernel requested but not available for this configuration")
+        return self.ws.get(name, ((nbytes + 3) // 4,), torch.int32) if nbytes else None
+
+    def _persistent_ws(self, fields):
+        """Workspace of the persistent decoder kernel for this argument block, or None when the step kernels run
+        (`use_persistent=False`, or `_persist_sync` finds the kernel not applicable)."""
+        if self.use_persistent is not None and not self.use_persistent:
             return None
-        return self.ws.get("gen.sync", ((nbytes + 3) // 4,), torch.int32)
+        sync = self._persist_sync("lvsr_attdec_persist_ws_bytes", self.lib.make("lvsr_attdec_args", **fields), "gen.sync")
+        if sync is None and self.use_persistent:
+            raise ValueError("persistent decoder kernel requested but not available for this configuration")
+        return sync
 
     def _persistent_bwd_ws(self, fwd_args):
-        """Workspace of the persistent backward kernel, or None (`use_persistent` / `use_persistent_bwd` False, outside its limits, or — on the CPU
-        emulator — work-groups not run concurrently)."""
+        """Workspace of the persistent backward kernel, or None (`use_persistent` / `use_persistent_bwd` False, or not applicable)."""
         # Default since round 3: 33.4 us per label against 41.5 for the four step kernels (profiles/r03_decoder_bwd_persist_probe.txt),
         # WSJ-base step 18.3 -> 17.4 ms.
         if self.use_persistent is False or self.use_persistent_bwd is False:
             return None
-        import ctypes as _ct
-        nbytes = int(self.lib._lvsr_attdec_bwd_persist_ws_bytes(_ct.byref(fwd_args)))
-        if self.lib.is_emulator and not self.lib.emulates_concurrency():
-            nbytes = 0
-        if nbytes == 0:
-            return None
-        return self.ws.get("gen.sync_bwd", ((nbytes + 3) // 4,), torch.int32)
+        return self._persist_sync("lvsr_attdec_bwd_persist_ws_bytes", fwd_args, "gen.sync_bwd")
+
+    def _plain(self, n, AW, AW_ld):
+        """lvsr_attdec_plain: the unpacked weights (parameter names n) a persistent kernel reads, and AW = attended @ [Wdi | Wdg]."""
+        p = self.store.p
+        return self.lib.make("lvsr_attdec_plain", Ws=p[n["Ws"]], Whg=p[n["Whg"]], Whh=p[n["Whh"]], AW=AW, AW_ld=AW_ld)
+
+    def _cluster_partials(self, query, fwd_args, B):
+        """(accH, accWe, accEb) of a persistent reverse walk: one row per work-group (`query`: work-groups per utterance of the
+        launch) — written, not accumulated, so nothing to clear."""
+        d, ws = self.d, self.ws
+        P = int(getattr(self.lib, "_" + query)(ctypes.byref(fwd_args)))
+        return (ws.get("gen.accH_p", (B * P, max(d.K, 1) * d.M)), ws.get("gen.accWe_p", (B * P, d.M)),
+                ws.get("gen.accEb_p", (B * P, 1)))
+
+    def _QR(self, sv, dWA_r):
+        """QR[:, b] = dWA_r_b (L,E) @ attended_b^T (E,T') for every utterance b, one batched launch: the readout's share of the
+        alignment gradient in the reassociated glimpse contraction of the persistent reverse walks."""
+        d, lib = self.d, self.lib
+        L, B, Tp = sv["L"], sv["B"], sv["Tp"]
+        QR = self.ws.get("gen.QR", (L, B, Tp))
+        lib.call("lvsr_sgemm_batched", lib.stream_for(QR), 0, 1, L, Tp, d.E, 1.0, ptr(dWA_r), B * d.E, d.E,
+                 ptr(sv["A"]), B * d.E, d.E, 0.0, ptr(QR), B * Tp, Tp, B)
+        return QR
 
     def check_persistent(self):
         """After a synchronisation point: raise if the persistent decoder kernel gave up waiting for its cluster."""
@@ -282,8 +366,8 @@ class SequenceGenerator(object):
         R1, R2, logits = self._readout(S2, WA2, L * B, "")
         cost = ws.get("gen.cost", (L, B))
         dlogits = ws.get("gen.dlogits", (L * B, d.V))
-        lib.call("lvsr_softmax_nll", lib.stream_for(cost), lib_ptr(logits), d.V, lib_ptr(labels), lib_ptr(ym), L * B, d.V,
-                 lib_ptr(cost), lib_ptr(dlogits), d.V, 1.0, None, 0)
+        lib.call("lvsr_softmax_nll", lib.stream_for(cost), ptr(logits), d.V, ptr(labels), ptr(ym), L * B, d.V,
+                 ptr(cost), ptr(dlogits), d.V, 1.0, None, 0)
         lm = self.language_model
         self._cost_has_lm = lm is not None
         if lm is not None:
@@ -292,10 +376,10 @@ class SequenceGenerator(object):
             # cost = -fused[label].  This is what `analyze` reports in the decode driver when `net.lm` is configured.
             lm_add = self._lm_lookahead(lm, labels, ym, L, B)
             fused = ws.get("gen.fused", (L * B, d.V))
-            lib.call("lvsr_shallow_fusion", lib.stream_for(cost), lib_ptr(logits), d.V, lib_ptr(lm_add), L * B, d.V, float(lm.am_beta),
-                     float(lm.lm_weight), int(lm.norm[0]), int(lm.norm[1]), int(lm.norm[2]), 1.0, lib_ptr(fused))
-            lib.call("lvsr_select_cost", lib.stream_for(cost), lib_ptr(fused), d.V, lib_ptr(labels), lib_ptr(ym), L * B, d.V, -1.0,
-                     lib_ptr(cost))
+            lib.call("lvsr_shallow_fusion", lib.stream_for(cost), ptr(logits), d.V, ptr(lm_add), L * B, d.V, float(lm.am_beta),
+                     float(lm.lm_weight), int(lm.norm[0]), int(lm.norm[1]), int(lm.norm[2]), 1.0, ptr(fused))
+            lib.call("lvsr_select_cost", lib.stream_for(cost), ptr(fused), d.V, ptr(labels), ptr(ym), L * B, d.V, -1.0,
+                     ptr(cost))
         self.last = dict(weights=W[1:], energies=bufs["EN"], states=S[:L], weighted_averages=WA)
         if save_for_backward:
             self._saved = dict(L=L, B=B, Tp=Tp, A=A, Am=Am, PA=PA, labels=labels, ym=ym, bufs=bufs,
@@ -310,35 +394,25 @@ class SequenceGenerator(object):
         d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
         xg = ws.get("gen.xg", (L * B, 3 * d.D))
         fb = ws.get("gen.fb", (L * B, d.FB)) if d.embed else None
-        self._feedback_fork(labels.view(-1), L * B, xg, fb)
-        S = ws.get("gen.S", (L + 1, B, d.D))
-        W = ws.get("gen.W", (L + 1, B, Tp))
+        self._feedback_forks(labels.view(-1), L * B, [(n, xg)], fb)
+        bufs = self._attdec_bufs("gen.", "", L, B, Tp, ZB=True, xg=xg, ymask=ym)
+        S, W = bufs["S"], bufs["W"]
         S[0].copy_(p[n["h0"]].unsqueeze(0).expand(B, d.D))     # initial_state tiled (recurrent.py:622-624)
         W[0].zero_()
         if d.conv:
             W[0, :, 0] = 1.0                                   # initial_glimpses (lvsr/bricks/attention.py:215-222)
-        Kc = max(d.K, 1)
-        bufs = dict(xg=xg, ymask=ym, S=S, W=W,
-                    pos=ws.get("gen.pos", (L + 1, B)) if (d.conv and self._prior()[0] != 0) else None,
-                    WA=ws.get("gen.WA", (L, B, d.E)), EN=ws.get("gen.EN", (L, B, Tp)), ZB=ws.get("gen.ZB", (L, B)),
-                    sW=ws.get("gen.sW", (L, B, d.M)),
-                    CV=ws.get("gen.CV", (L, B, Kc, Tp)) if d.conv else None,
-                    U=ws.get("gen.U", (L, B, d.D)), R=ws.get("gen.R", (L, B, d.D)), C=ws.get("gen.C", (L, B, d.D)),
-                    RH=ws.get("gen.RH", (L, B, d.D)), sg=ws.get("gen.sg", (B, 2 * d.D)), xin=ws.get("gen.xin", (B, d.D)),
-                    ep=ws.get("gen.ep", (B, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
         fields = self._attdec_fields(pk, A, PA, Am, L, B, bufs, phases=3, step0=0, broadcast=False)
         sync = self._persistent_ws(fields)
         if sync is not None:
             # one persistent launch for the whole label loop (csrc/decoder_persist.hip): a memset and a kernel, no graph needed
-            import ctypes as _ct
             fwd_args = lib.make("lvsr_attdec_args", **fields)
             # gate inputs of the glimpse, reassociated: AW = attended @ [fork_inputs.W | fork_gate_inputs.W] once per batch
             wd = ws.get("gen.Wd_cat", (d.E, 3 * d.D))
             AW, AW_ld = self._AW(Tp, B)
             lib.sgemm(A.view(Tp * B, d.E), wd, AW)
-            plain = lib.make("lvsr_attdec_plain", Ws=p[n["Ws"]], Whg=p[n["Whg"]], Whh=p[n["Whh"]], AW=AW, AW_ld=AW_ld)
-            lib.call("lvsr_attdec_fwd_persistent", lib.stream_for(S), _ct.byref(fwd_args), _ct.byref(plain), lib_ptr(sync), 0)
-            lib.call("lvsr_attdec_glimpses", lib.stream_for(S), _ct.byref(fwd_args))
+            lib.call("lvsr_attdec_fwd_persistent", lib.stream_for(S), ctypes.byref(fwd_args), ctypes.byref(self._plain(n, AW, AW_ld)),
+                     ptr(sync), 0)
+            lib.call("lvsr_attdec_glimpses", lib.stream_for(S), ctypes.byref(fwd_args))
         else:
             self._ensure_packs(pk)
             fwd_args = lib.run("lvsr_attdec_fwd", "lvsr_attdec_args", S, self.use_graph, **fields)
@@ -400,15 +474,15 @@ class SequenceGenerator(object):
                 wn, bn, width = self.pm_hidden[j]
                 xin, pre = sv["pm_acts"][j]
                 dpre = ws.get("gen.pm_dpre%d" % j, (nrows, width))
-                lib.call("lvsr_act_bwd", lib.stream_for(dpre), ACT_KIND[d.act], lib_ptr(pre), width, lib_ptr(dR2), width, nrows, width,
-                         lib_ptr(dpre), width)
+                lib.call("lvsr_act_bwd", lib.stream_for(dpre), ACT_KIND[d.act], ptr(pre), width, ptr(dR2), width, nrows, width,
+                         ptr(dpre), width)
                 wgrad(xin, dpre, g[wn])
                 colsum(dpre, g[bn])
                 dR2 = ws.get("gen.pm_dx%d" % j, (nrows, xin.shape[1]))
                 lib.sgemm(dpre, p[wn], dR2, transB=True)
             dR1 = ws.get("gen.dR1", (nrows, d.P))
-            lib.call("lvsr_act_bwd", lib.stream_for(dR1), ACT_KIND[d.act], lib_ptr(R1), d.P, lib_ptr(dR2), d.Pout, nrows, d.P,
-                     lib_ptr(dR1), d.P)
+            lib.call("lvsr_act_bwd", lib.stream_for(dR1), ACT_KIND[d.act], ptr(R1), d.P, ptr(dR2), d.Pout, nrows, d.P,
+                     ptr(dR1), d.P)
             colsum(dR1, g[n["bpm"]])
         else:
             dR1 = dlogits
@@ -421,7 +495,6 @@ class SequenceGenerator(object):
             dS_r = self._merge_states_backward(S2, dR1, gws, group)
         rb = self._backward_recurrent(sv, dWA_r, dS_r, gws, group)
         accH, accWe, accEb, DCV, dPA, DWA = rb["accH"], rb["accWe"], rb["accEb"], rb["DCV"], rb["dPA"], rb["DWA"]
-        import ctypes
         st = lib.stream_for(dPA)
         colsum(accWe, g[n["we"]].view(-1))
         if d.energy_bias:
@@ -430,7 +503,7 @@ class SequenceGenerator(object):
             colsum(accH, g[n["handler"]].view(-1))
             # partial sums per chunk of (label, utterance) rows: at most one chunk per row (large per-GPU batches outgrow gemm_ws)
             fws = ws.get("gen.filter_ws", (max(1 << 20, L * B * d.K * (2 * d.c + 1)),))
-            lib.call("lvsr_attdec_filter_grad", st, ctypes.byref(rb["fwd_args"]), lib_ptr(DCV), lib_ptr(g[n["filters"]]), lib_ptr(fws),
+            lib.call("lvsr_attdec_filter_grad", st, ctypes.byref(rb["fwd_args"]), ptr(DCV), ptr(g[n["filters"]]), ptr(fws),
                      fws.numel() * 4)
         # ---- attended: preprocess backward + glimpse backward
         A2, dPA2 = sv["A"].view(Tp * B, d.E), dPA.view(Tp * B, d.M)
@@ -440,8 +513,8 @@ class SequenceGenerator(object):
         lib.sgemm(dPA2, p[n["Wpre"]], dA.view(Tp * B, d.E), transB=True)
         W = bufs["W"]
         # dA[:, b, :] += alpha_b^T (T',L) @ dwa_b (L,E) for every utterance b: one batched launch
-        lib.call("lvsr_sgemm_batched", lib.stream_for(dA), 1, 0, Tp, d.E, L, 1.0, lib_ptr(W[1:]), B * Tp, Tp,
-                 lib_ptr(DWA), B * d.E, d.E, 1.0, lib_ptr(dA), B * d.E, d.E, B)
+        lib.call("lvsr_sgemm_batched", lib.stream_for(dA), 1, 0, Tp, d.E, L, 1.0, ptr(W[1:]), B * Tp, Tp,
+                 ptr(DWA), B * d.E, d.E, 1.0, ptr(dA), B * d.E, d.E, B)
         return dA
 
     def _backward_recurrent(self, sv, dWA_r, dS_r, gws, group=None):
@@ -456,7 +529,6 @@ class SequenceGenerator(object):
         nslice = (d.M + ATT_MS - 1) // ATT_MS
         ntile = (Tp + 63) // 64
         Kc = max(d.K, 1)
-        import ctypes
         wgrad, colsum = lib.weight_grad_calls(group, gws)
         DXG = ws.get("gen.DXG", (nrows, 3 * d.D))
         # The glimpse contraction is reassociated (as in the persistent forward): q = DXG . AW + QR — the kernels need no dwa and do
@@ -471,23 +543,17 @@ class SequenceGenerator(object):
         AW, AW_ld = self._AW(Tp, B)
         if not sv.get("AW_valid"):
             lib.sgemm(sv["A"].view(Tp * B, d.E), wd, AW)
-        QR = ws.get("gen.QR", (L, B, Tp))
-        lib.call("lvsr_sgemm_batched", lib.stream_for(QR), 0, 1, L, Tp, d.E, 1.0, lib_ptr(dWA_r), B * d.E, d.E,
-                 lib_ptr(sv["A"]), B * d.E, d.E, 0.0, lib_ptr(QR), B * Tp, Tp, B)
+        QR = self._QR(sv, dWA_r)
         fwd_args = lib.make("lvsr_attdec_args", **sv["fields"])
         psync = self._persistent_bwd_ws(fwd_args)
         if psync is not None:
             # the whole reverse walk as one persistent launch (csrc/decoder_persist_bwd.hip); its handler / energy-vector / bias
             # gradient partials come one row per work-group — written, not accumulated: nothing but dPA and ds to clear
-            P = int(lib._lvsr_attdec_bwd_persist_clusters(ctypes.byref(fwd_args)))        # work-groups per utterance of the launch
-            accH = ws.get("gen.accH_p", (B * P, Kc * d.M))
-            accWe = ws.get("gen.accWe_p", (B * P, d.M))
-            accEb = ws.get("gen.accEb_p", (B * P, 1))
+            accH, accWe, accEb = self._cluster_partials("lvsr_attdec_bwd_persist_clusters", fwd_args, B)
             bw = lib.make("lvsr_attdec_bwd_args", dS_r=dS_r, DXG=DXG, DSW=DSW, DCV=DCV, dPA=dPA, accH=accH, accWe=accWe, accEb=accEb,
                           ds=ds, AW=AW, QR=QR, AW_ld=AW_ld)
             bw.f = fwd_args
-            plain = lib.make("lvsr_attdec_plain", Ws=p[n["Ws"]], Whg=p[n["Whg"]], Whh=p[n["Whh"]], AW=AW, AW_ld=AW_ld)
-            lib.call("lvsr_attdec_bwd_persistent", lib.stream_for(ds), ctypes.byref(bw), ctypes.byref(plain), lib_ptr(psync))
+            lib.call("lvsr_attdec_bwd_persistent", lib.stream_for(ds), ctypes.byref(bw), ctypes.byref(self._plain(n, AW, AW_ld)), ptr(psync))
         else:
             self._ensure_packs(pk)
             accH = ws.get("gen.accH", (B * ntile, Kc * d.M), zero=True)
@@ -513,32 +579,10 @@ class SequenceGenerator(object):
         colsum(ds, g[n["h0"]])
         colsum(dpc, g[n["bfi"]])
         colsum(dg, g[n["bfg"]])
-        st = lib.stream_for(ds)
-        labels_flat = sv["labels"].view(-1)
-        if d.embed:
-            fb = sv["fb"]
-            wgrad(fb, dpc, g[n["Wfi"]])
-            wgrad(fb, dg, g[n["Wfg"]])
-            dfb = ws.get("gen.dfb", (nrows, d.FB))
-            lib.sgemm(dpc, p[n["Wfi"]], dfb, transB=True)
-            lib.sgemm(dg, p[n["Wfg"]], dfb, transB=True, beta=1.0)
-            lib.call("lvsr_scatter_add_rows", st, lib_ptr(dfb), d.FB, lib_ptr(labels_flat), nrows, d.V + 1, d.FB,
-                     lib_ptr(g[n["table"]]), d.FB, 0.0)
-        else:
-            lib.call("lvsr_scatter_add_rows", st, lib_ptr(dpc), 3 * d.D, lib_ptr(labels_flat), nrows, d.FB, d.D,
-                     lib_ptr(g[n["Wfi"]]), d.D, 0.0)
-            lib.call("lvsr_scatter_add_rows", st, lib_ptr(dg), 3 * d.D, lib_ptr(labels_flat), nrows, d.FB, 2 * d.D,
-                     lib_ptr(g[n["Wfg"]]), 2 * d.D, 0.0)
+        self._feedback_forks_backward(0, n, sv, DXG, ws.get("gen.dfb", (nrows, d.FB)) if d.embed else None, wgrad)
         return dict(accH=accH, accWe=accWe, accEb=accEb, DCV=DCV, dPA=dPA, DWA=DWA, fwd_args=fwd_args)
 
-
-def lib_ptr(t):
-    from ..native import ptr
-    return ptr(t)
-
-
-# ---- generation mode (what BeamSearch drives: libs/blocks/blocks/search.py:97-142) -----------------------
-def _generation_methods():
+    # ---- generation mode (what BeamSearch drives: libs/blocks/blocks/search.py:97-142) -----------------------
     def init_generation(self, attended, attended_mask):
         """context_computer (search.py:97-104): keep the single utterance's contexts; every hypothesis of the
         beam reads them with a zero batch stride (no tiling as in search.py:336-338)."""
@@ -555,106 +599,7 @@ def _generation_methods():
             self._gen = dict(Tp=Tp, A=A, Am=Am, PA=PA, N=N, lengths=self.ws.get("gen.glen", (N,), torch.int32))
             self._gen["lengths"].copy_(Am.sum(dim=0).to(torch.int32))
 
-    def generation_initial_states(self, n=1):
-        """initial_state_computer (search.py:106-110): states = tiled initial_state (recurrent.py:622-624),
-        weights = initial glimpses (lvsr/bricks/attention.py:215-222), outputs = num_phonemes
-        (recognizer.py:286, sequence_generators.py:793-795), step = 0."""
-        d, p, n_ = self.d, self.store.p, self.n
-        Tp = self._gen["Tp"]
-        S = p[n_["h0"]].unsqueeze(0).expand(n, d.D).clone()
-        W = torch.zeros(n, Tp, dtype=torch.float32, device=S.device)
-        if d.conv:
-            W[:, 0] = 1.0
-        # initial outputs: SoftmaxEmitter(initial_output=num_phonemes) (recognizer.py:286); with a language model the
-        # emitter is LMEmitter whose initial_outputs are zeros (language_models.py:172-175)
-        first = 0 if self.language_model is not None else d.V
-        return dict(states=S, weights=W, step=0, outputs=numpy.full((n,), first, dtype=numpy.int64))
-
-    def _gen_run(self, S, W, step0, phases, outputs=None):
-        d, lib, ws, g = self.d, self.lib, self.ws, self._gen
-        n, Tp = int(S.shape[0]), g["Tp"]
-        pk = self._packed()
-        # the buffer views and the argument block of a (beam width, phases) pair are built once per set of contexts: the
-        # search loop calls this twice per emitted character and the Python bookkeeping was ~0.4 ms of each step
-        key = (n, phases, g["A"].data_ptr(), g["PA"].data_ptr(), g["Am"].data_ptr(), Tp, id(pk))
-        ent = self._gen_cache.get(key)
-        if ent is None or ent["generation"] != ws.generation:
-            tag = ".n%d" % n
-            Sb = ws.get("gs.S" + tag, (2, n, d.D))
-            Wb = ws.get("gs.W" + tag, (2, n, Tp))
-            xg = y = fb = None
-            if phases & 2:
-                xg = ws.get("gs.xg" + tag, (n, 3 * d.D))
-                y = ws.get("gs.y" + tag, (n,), torch.int64)
-                fb = ws.get("gs.fb" + tag, (n, d.FB)) if d.embed else None
-            Kc = max(d.K, 1)
-            bufs = dict(xg=xg, ymask=None, S=Sb, W=Wb,
-                        pos=ws.get("gs.pos" + tag, (2, n)) if (d.conv and self._prior()[0] != 0) else None,
-                        WA=ws.get("gs.WA" + tag, (1, n, d.E)), EN=ws.get("gs.EN" + tag, (1, n, Tp)), ZB=None,
-                        sW=ws.get("gs.sW" + tag, (1, n, d.M)), CV=ws.get("gs.CV" + tag, (1, n, Kc, Tp)) if d.conv else None,
-                        U=ws.get("gs.U" + tag, (1, n, d.D)), R=ws.get("gs.R" + tag, (1, n, d.D)),
-                        C=ws.get("gs.C" + tag, (1, n, d.D)), RH=ws.get("gs.RH" + tag, (1, n, d.D)),
-                        sg=ws.get("gs.sg" + tag, (n, 2 * d.D)), xin=ws.get("gs.xin" + tag, (n, d.D)),
-                        ep=ws.get("gs.ep" + tag, (n, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
-            fields = self._attdec_fields(pk, g["A"], g["PA"], g["Am"], 1, n, bufs, phases=phases, step0=int(step0), broadcast=True)
-            ent = dict(generation=ws.generation, bufs=bufs, args=lib.make("lvsr_attdec_args", **fields), y=y, fb=fb, xg=xg,
-                       S0=Sb[0], W0=Wb[0])
-            if len(self._gen_cache) > 64:
-                self._gen_cache.clear()
-            self._gen_cache[key] = ent
-        ent["S0"].copy_(S)
-        ent["W0"].copy_(W)
-        if phases & 2:
-            ent["y"].copy_(torch.as_tensor(outputs, dtype=torch.int64), non_blocking=False)
-            self._feedback_fork(ent["y"], n, ent["xg"], ent["fb"])
-        ent["args"].step0 = int(step0)
-        lib.call("lvsr_attdec_fwd", lib.stream_for(ent["S0"]), ctypes.byref(ent["args"]), 0)
-        return ent["bufs"]
-
-    def generation_logprobs(self, S, W, step0):
-        """logprobs_computer (search.py:126-134): take_glimpses -> readout -> -log_softmax; (n,V) device tensor."""
-        d, lib, ws = self.d, self.lib, self.ws
-        n = int(S.shape[0])
-        bufs = self._gen_run(S, W, step0, phases=1)
-        _, _, logits = self._readout(bufs["S"][0], bufs["WA"][0], n, ".gen%d" % n)
-        nl = ws.get("gs.neglogp.n%d" % n, (n, d.V))
-        lm = self.language_model
-        if lm is not None:
-            # ShallowFusionReadout + LMEmitter: the fused readout IS the log-probability; costs = -readout
-            add = ws.get("gs.lm_add.n%d" % n, (n, d.V))
-            add.copy_(lm.device_add)
-            lib.call("lvsr_shallow_fusion", lib.stream_for(nl), lib_ptr(logits), d.V, lib_ptr(add), n, d.V, lm.am_beta,
-                     lm.lm_weight, int(lm.norm[0]), int(lm.norm[1]), int(lm.norm[2]), -1.0, lib_ptr(nl))
-            return nl
-        lib.call("lvsr_softmax_nll", lib.stream_for(nl), lib_ptr(logits), d.V, None, None, n, d.V, None, None, 0, 1.0,
-                 lib_ptr(nl), d.V)
-        return nl
-
-    def generation_next_states(self, S, W, step0, outputs):
-        """next_state_computer (search.py:112-124): take_glimpses AGAIN on the re-arranged hypotheses (the window
-        of the location prior depends on the batch it is computed for) + compute_states with the chosen outputs."""
-        bufs = self._gen_run(S, W, step0, phases=3, outputs=outputs)
-        # hand the new states out in buffers no later generation call writes to (the step buffers are reused by the very
-        # next generation_logprobs, which would otherwise overwrite the alignments the caller still holds)
-        n = int(S.shape[0])
-        So = self.ws.get("gs.Sout.n%d" % n, tuple(bufs["S"][1].shape))
-        Wo = self.ws.get("gs.Wout.n%d" % n, tuple(bufs["W"][1].shape))
-        So.copy_(bufs["S"][1])
-        Wo.copy_(bufs["W"][1])
-        return dict(states=So, weights=Wo, step=int(step0) + 1,
-                    weighted_averages=bufs["WA"][0], outputs=numpy.asarray(outputs))
-
-    return dict(init_generation=init_generation, generation_initial_states=generation_initial_states, _gen_run=_gen_run,
-                generation_logprobs=generation_logprobs, generation_next_states=generation_next_states)
-
-
-for _k, _v in _generation_methods().items():
-    setattr(SequenceGenerator, _k, _v)
-SequenceGenerator.language_model = None
-
-
-# ---- free-running generation: SequenceGenerator.generate / initial_states, SoftmaxEmitter.emit ---------------------------
-def _sampling_methods():
+    # ---- free-running generation: SequenceGenerator.generate / initial_states, SoftmaxEmitter.emit ---------------------------
     def initial_states(self, batch_size, attended=None, attended_mask=None):
         """BaseSequenceGenerator.initial_states (sequence_generators.py:404-422): initial values of the `generate` states:
         states = tiled initial_state (recurrent.py:622-624), outputs = SoftmaxEmitter.initial_outputs (num_phonemes,
@@ -684,8 +629,8 @@ def _sampling_methods():
         u = self._uniforms((n,), uniforms, seed, x.device)
         out = torch.empty(n, dtype=torch.int64, device=x.device)
         cost = torch.empty(n, dtype=torch.float32, device=x.device)
-        lib.call("lvsr_softmax_emit", lib.stream_for(x), lib_ptr(x), int(x.stride(0)), lib_ptr(u), n, int(x.shape[1]), lib_ptr(out),
-                 lib_ptr(cost))
+        lib.call("lvsr_softmax_emit", lib.stream_for(x), ptr(x), int(x.stride(0)), ptr(u), n, int(x.shape[1]), ptr(out),
+                 ptr(cost))
         return out, cost
 
     def _uniforms(self, shape, uniforms, seed, dev):
@@ -723,19 +668,13 @@ def _sampling_methods():
         PA = self.preprocess(A)
         dev = A.device
         u = self._uniforms((N, B), uniforms, seed, dev)
-        Kc = max(d.K, 1)
-        pos_needed = d.conv and self._prior()[0] != 0
+        pos_needed = self._pos_needed()
         S = ws.get("sg.S", (N + 1, B, d.D))
         W = ws.get("sg.W", (N + 1, B, Tp))
         first = self.initial_states(B, attended=A)
         S[0].copy_(first["states"])
         W[0].copy_(first["weights"])
-        full = dict(xg=ws.get("sg.xg", (N, B, 3 * d.D)), S=S, W=W, pos=ws.get("sg.pos", (N + 1, B)) if pos_needed else None,
-                    WA=ws.get("sg.WA", (N, B, d.E)), EN=ws.get("sg.EN", (N, B, Tp)), sW=ws.get("sg.sW", (N, B, d.M)),
-                    CV=ws.get("sg.CV", (N, B, Kc, Tp)) if d.conv else None, U=ws.get("sg.U", (N, B, d.D)),
-                    R=ws.get("sg.R", (N, B, d.D)), C=ws.get("sg.C", (N, B, d.D)), RH=ws.get("sg.RH", (N, B, d.D)))
-        shared = dict(ymask=None, ZB=None, sg=ws.get("sg.sg", (B, 2 * d.D)), xin=ws.get("sg.xin", (B, d.D)),
-                      ep=ws.get("sg.ep", (B, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
+        full = self._attdec_bufs("sg.", "", N, B, Tp, S=S, W=W, xg=ws.get("sg.xg", (N, B, 3 * d.D)), ymask=None)
         outputs = ws.get("sg.outputs", (N, B), torch.int64)
         costs = ws.get("sg.costs", (N, B))
         fb = ws.get("sg.fb", (B, d.FB)) if d.embed else None
@@ -743,30 +682,19 @@ def _sampling_methods():
             full["pos"][0].zero_()
         st = lib.stream_for(S)
         for t in range(N):
-            bufs = {k: (None if v is None else v[t:]) for k, v in full.items()}
-            bufs.update(shared)
+            # step t works on the slots from t on; the scratch of a step (sg, xin, ep) is shared by all of them
+            bufs = {k: v if v is None or k in ("sg", "xin", "ep") else v[t:] for k, v in full.items()}
             skip = 4 if pos_needed else 0
             fa = self._attdec_fields(pk, A, PA, Am, 1, B, bufs, phases=1 | skip, step0=t, broadcast=False)
             lib.call("lvsr_attdec_fwd", st, ctypes.byref(lib.make("lvsr_attdec_args", **fa)), 0)
             ra = self._readout_step_args(S[t], full["WA"][t], B, uniforms=u[t], outputs=outputs[t], costs=costs[t])
             lib.call("lvsr_readout_step", st, ctypes.byref(ra))
-            self._feedback_fork(outputs[t], B, full["xg"][t], fb)
+            self._feedback_forks(outputs[t], B, [(n, full["xg"][t])], fb)
             fg = self._attdec_fields(pk, A, PA, Am, 1, B, bufs, phases=2, step0=t, broadcast=False)
             lib.call("lvsr_attdec_fwd", st, ctypes.byref(lib.make("lvsr_attdec_args", **fg)), 0)
         return dict(states=S[1:], outputs=outputs, weighted_averages=full["WA"], weights=W[1:], energies=full["EN"], costs=costs)
 
-    return dict(initial_states=initial_states, emit=emit, _uniforms=_uniforms, generate=generate)
-
-
-for _k, _v in _sampling_methods().items():
-    setattr(SequenceGenerator, _k, _v)
-
-
-# ---- device-resident beam search (csrc/beam.hip): state of one search + the launches of one position ------------------
-CTL = dict(nlive=0, pos=1, done=2, nfin=3, patience=4, nsel=5, err=6, steps=7)
-
-
-def _beam_methods():
+    # ---- device-resident beam search (csrc/beam.hip): state of one search + the launches of one position ------------------
     def beam_begin(self, K, eol, max_length, ignore_first_eol=False, char_discount=0.0, round_to_inf=1e9, stop_on="patience",
                    force_merge=False):
         """Allocate (once per (K, T', max_length)) and reset the device state of a beam search over the contexts set by
@@ -800,23 +728,14 @@ def _beam_methods():
         K_one, K = K, R            # below, K counts ROWS of the state buffers; K_one is the beam size
         i32, i64, f64 = torch.int32, torch.int64, torch.float64
         fin_cap = 2 * K_one if stop_on == "patience" else K_one * (max_length + 1)
-        Kc = max(d.K, 1)
-        pos_needed = d.conv and self._prior()[0] != 0
+        pos_needed = self._pos_needed()
         SW = self._state_width()
         stacked = d.n_dec > 1          # bricks/generator_stack.py: pass B is the attention block and one GRU block per layer
 
-        def attbufs(which, phases):
+        def attbufs(which, fork):
             t = tag + which
-            return dict(xg=ws.get("bs.xg" + t, (K, 3 * d.D)) if phases & 2 else None, ymask=None,
-                        S=ws.get("bs.S" + t, (2, K, SW)), W=ws.get("bs.W" + t, (2, K, Tp)),
-                        pos=ws.get("bs.pos" + t, (2, K)) if pos_needed else None,
-                        WA=ws.get("bs.WA" + t, (1, K, d.E)), EN=ws.get("bs.EN" + t, (1, K, Tp)), ZB=None,
-                        sW=ws.get("bs.sW" + t, (1, K, d.M)), CV=ws.get("bs.CV" + t, (1, K, Kc, Tp)) if d.conv else None,
-                        U=ws.get("bs.U" + t, (1, K, d.D)), R=ws.get("bs.R" + t, (1, K, d.D)),
-                        C=ws.get("bs.C" + t, (1, K, d.D)), RH=ws.get("bs.RH" + t, (1, K, d.D)),
-                        sg=ws.get("bs.sg" + t, (K, 2 * d.D)), xin=ws.get("bs.xin" + t, (K, d.D)),
-                        ep=ws.get("bs.ep" + t, (K, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
-        A_, B_ = attbufs("a", 1), attbufs("b", 3)
+            return self._attdec_bufs("bs.", t, 1, K, Tp, xg=ws.get("bs.xg" + t, (K, 3 * d.D)) if fork else None, ymask=None)
+        A_, B_ = attbufs("a", False), attbufs("b", True)
         gshape = (lambda *dims: dims) if G == 1 else (lambda *dims: (G,) + dims)
         st = dict(K=K_one, rows=K, groups=G, Tp=Tp, max_length=int(max_length), limits=limits, fin_cap=fin_cap, A=A_, B=B_,
                   ctl=ws.get("bs.ctl" + tag, gshape(16), i32), fctl=ws.get("bs.fctl" + tag, gshape(4)),
@@ -878,8 +797,8 @@ def _beam_methods():
         R1 = ws.get("bs.R1" + tag, (K, d.P)) if (K >= self.MERGE_ROWS or force_merge) else None
         if R1 is not None:
             ro = self._readout_packs()
-            st["merge"] = (lib_ptr(A_["S"][0]), int(A_["S"][0].stride(0)), lib_ptr(A_["WA"][0]), int(A_["WA"][0].stride(0)), K, SW, d.E, d.P,
-                           lib_ptr(ro["Wms"]), lib_ptr(ro["Wmw"]), lib_ptr(p[n_["bpm"]] if d.post_merge else p[n_["bro"]]), lib_ptr(R1), int(R1.stride(0)))
+            st["merge"] = (ptr(A_["S"][0]), int(A_["S"][0].stride(0)), ptr(A_["WA"][0]), int(A_["WA"][0].stride(0)), K, SW, d.E, d.P,
+                           ptr(ro["Wms"]), ptr(ro["Wmw"]), ptr(p[n_["bpm"]] if d.post_merge else p[n_["bro"]]), ptr(R1), int(R1.stride(0)))
         st["readout"] = self._readout_step_args(A_["S"][0], A_["WA"][0], K, neglogp=st["neglogp"],
                                                 lm_add=L.get("add_live") if lm is not None else None, R1=R1)
         # ---- reset: one live hypothesis, replicated over the K rows
@@ -960,7 +879,7 @@ def _beam_methods():
             self._beam_step_run(st)
         else:
             if d.embed:          # lookup feedback needs the fork's GEMMs; one-hot feedback was gathered by the select launch
-                self._feedback_fork(st["chars"], K, B_["xg"], st["fb"])
+                self._feedback_forks(st["chars"], K, [(self.n, B_["xg"])], st["fb"])
             lib.call("lvsr_attdec_fwd", lib.stream_for(B_["S"]), ctypes.byref(st["argsB"]), 0)
         if st["on_dev_lm"]:
             self._beam_lm_step(st, K)
@@ -969,42 +888,24 @@ def _beam_methods():
     def _beam_lm_step(self, st, K):
         """Language-model transition on the chosen characters + look-ahead costs of the new state sets (lvsr_fst_lm_step*)."""
         lib, L, lm = self.lib, st["lm"], self.language_model
-        if st["groups"] > 1:       # the rows of finished searches are skipped (their characters are stale)
-            lib.call("lvsr_fst_lm_step_groups", lib.stream_for(L["states_sel"]), ctypes.byref(lm._fst), lib_ptr(L["states_sel"]),
-                     lib_ptr(L["weights_sel"]), lib_ptr(st["chars"]), K, lib_ptr(L["states_new"]), lib_ptr(L["weights_new"]),
-                     lib_ptr(L["add_new"]), lib_ptr(lm._err), lib_ptr(st["ctl"]), st["K"])
-        else:
-            lib.call("lvsr_fst_lm_step", lib.stream_for(L["states_sel"]), ctypes.byref(lm._fst), lib_ptr(L["states_sel"]),
-                     lib_ptr(L["weights_sel"]), lib_ptr(st["chars"]), K, lib_ptr(L["states_new"]), lib_ptr(L["weights_new"]),
-                     lib_ptr(L["add_new"]), lib_ptr(lm._err))
-
-    def beam_step(self):
-        """All launches of one position as one replayed hipGraph (captured on the second step of a search shape)."""
-        st = self._beam
-
-        def enqueue():
-            self.beam_costs()
-            self.beam_select()
-            self.beam_advance()
-        self.lib.region(self, st["key"], st["ctl"], enabled=self.use_graph, volatile=st["volatile"], drain=False).run(enqueue)
+        grouped = st["groups"] > 1       # the rows of finished searches are skipped (their characters are stale)
+        args = [ctypes.byref(lm._fst), ptr(L["states_sel"]), ptr(L["weights_sel"]), ptr(st["chars"]), K, ptr(L["states_new"]),
+                ptr(L["weights_new"]), ptr(L["add_new"]), ptr(lm._err)] + ([ptr(st["ctl"]), st["K"]] if grouped else [])
+        lib.call("lvsr_fst_lm_step_groups" if grouped else "lvsr_fst_lm_step", lib.stream_for(L["states_sel"]), *args)
 
     def beam_steps(self, n):
         """n consecutive positions as ONE replayed hipGraph (the position counter lives on the device, so the graph does not
         depend on where the search stands): the driver looks at the control block every n positions anyway."""
         st = self._beam
-        if n == 1:
-            return self.beam_step()
 
         def enqueue():
             for _ in range(n):
                 self.beam_costs()
                 self.beam_select()
                 self.beam_advance()
-        self.lib.region(self, (st["key"], "x%d" % n), st["ctl"], enabled=self.use_graph, volatile=st["volatile"], drain=False).run(enqueue)
+        key = st["key"] if n == 1 else (st["key"], "x%d" % n)
+        self.lib.region(self, key, st["ctl"], enabled=self.use_graph, volatile=st["volatile"], drain=False).run(enqueue)
 
-    return dict(beam_begin=beam_begin, _beam_begin=_beam_begin, beam_costs=beam_costs, beam_select=beam_select, beam_advance=beam_advance,
-                _beam_lm_step=_beam_lm_step, beam_step=beam_step, beam_steps=beam_steps, _readout_step_args=_readout_step_args)
-
-
-for _k, _v in _beam_methods().items():
-    setattr(SequenceGenerator, _k, _v)
+    def beam_step(self):
+        """All launches of one position as one replayed hipGraph (captured on the second step of a search shape)."""
+        self.beam_steps(1)

@@ -26,7 +26,8 @@ import ctypes
 import torch
 
 from ..spec import decoder_layer_names
-from .generator import SequenceGenerator, ATT_MS, NORMALIZER_KIND, lib_ptr
+from ..native import ptr
+from .generator import SequenceGenerator, ATT_MS
 
 _LAYER_KEYS = ("Ws", "Wdi", "Wdg", "Whh", "Whg", "h0", "Wfi", "bfi", "Wfg", "bfg", "Wms")
 
@@ -113,60 +114,26 @@ class StackedSequenceGenerator(SequenceGenerator):
         return ent
 
     # ---- argument blocks ---------------------------------------------------------------------------------------------
-    def _strides(self, B, broadcast):
-        d = self.d
-        if broadcast:
-            return dict(A_ts=d.E, A_bs=0, PA_ts=d.M, PA_bs=0, Am_ts=1, Am_bs=0)
-        return dict(A_ts=B * d.E, A_bs=d.E, PA_ts=B * d.M, PA_bs=d.M, Am_ts=B, Am_bs=1)
-
-    def _att_fields(self, pk, A, PA, Am, L, B, bufs, phases, step0, broadcast, groups=0, group_Tp=None):
-        """The attention over the concatenated states: the one-layer block with D = n*D and no GRU part.  groups: batched beam
-        search (rows [g B/groups, ...) read utterance g: lvsr_attdec_args.group_rows)."""
-        d, p, n = self.d, self.store.p, self.n
-        kind, pp = self._prior()
-        f = dict(Tp=int(A.shape[0]), B=B, L=L, E=d.E, D=d.D_tot, M=d.M, K=d.K, c=d.c, prior_type=kind, step0=step0,
-                 phases=phases, p0=pp[0], p1=pp[1], p2=pp[2], p3=pp[3], A=A, PA=PA, Am=Am, Ws_p=pk["Ws"], w_e=p[n["we"]],
-                 normalizer=NORMALIZER_KIND[d.normalizer], e_bias=p[n["eb"]] if d.energy_bias else None,
-                 filters=p[n["filters"]] if d.conv else None, handler=p[n["handler"]] if d.conv else None)
-        if groups:
-            f.update(A_ts=groups * d.E, A_bs=d.E, PA_ts=groups * d.M, PA_bs=d.M, Am_ts=groups, Am_bs=1,
-                     group_rows=B // groups, step_stride=16, group_Tp=group_Tp)
-        else:
-            f.update(self._strides(B, broadcast))
-        f.update(bufs)
-        return f
-
     def _attdec_fields(self, pk, A, PA, Am, L, B, bufs, phases, step0, broadcast, groups=0, group_Tp=None):
+        """The attention over the concatenated states: the one-layer block with D = n*D and no GRU part."""
         assert not phases & 2, "a stacked decoder has no one-block GRU step"
-        return self._att_fields(pk, A, PA, Am, L, B, {k: v for k, v in bufs.items() if k not in ("U", "R", "C", "RH", "sg", "xin", "xg")},
-                                phases, step0, broadcast, groups=groups, group_Tp=group_Tp)
+        f = self._att_fields(A, PA, Am, L, B, self.d.D_tot, {k: v for k, v in bufs.items() if k not in ("U", "R", "C", "RH", "sg", "xin", "xg")},
+                             phases, step0, broadcast, groups, group_Tp)
+        f["Ws_p"] = pk["Ws"]
+        return f
 
     def _layer_fields(self, l, pk, A, PA, Am, L, B, bufs, broadcast):
         """GRU layer l: the one-layer block with the GRU part only, E = width of [glimpse | state below], no location prior."""
         d = self.d
         f = dict(Tp=int(A.shape[0]), B=B, L=L, E=self._E(l), D=d.D, M=d.M, K=0, c=0, prior_type=0, step0=0, phases=2,
-                 p0=0.0, p1=0.0, p2=0.0, p3=0.0, A=A, PA=PA, Am=Am, normalizer=0,
-                 Whg_p=pk["Whg%d" % l], Whh_p=pk["Whh%d" % l], Wdi_p=pk["Wdi%d" % l], Wdg_p=pk["Wdg%d" % l])
+                 p0=0.0, p1=0.0, p2=0.0, p3=0.0, A=A, PA=PA, Am=Am, normalizer=0, **self._gru_fields(pk, l))
         f.update(self._strides(B, broadcast))
         f.update(bufs)
         return f
 
-    def _feedback_forks(self, labels_flat, nrows, xgs, fb_buf=None):
-        """xgs[l] (nrows,3D) = fork#l(feedback(labels)) (sequence_generators.py:263-264 with the stack's sequence names)."""
-        d, p, lib = self.d, self.store.p, self.lib
-        st = lib.stream_for(xgs[0])
-        if d.embed:
-            lib.call("lvsr_gather_rows", st, lib_ptr(p[self.n["table"]]), d.FB, lib_ptr(labels_flat), nrows, d.V + 1, d.FB,
-                     None, lib_ptr(fb_buf), d.FB)
-        for n, xg in zip(self.nl, xgs):
-            if d.embed:
-                lib.sgemm(fb_buf, p[n["Wfi"]], xg[:, : d.D], bias=p[n["bfi"]])
-                lib.sgemm(fb_buf, p[n["Wfg"]], xg[:, d.D:], bias=p[n["bfg"]])
-            else:
-                lib.call("lvsr_gather_rows", st, lib_ptr(p[n["Wfi"]]), d.D, lib_ptr(labels_flat), nrows, d.FB, d.D,
-                         lib_ptr(p[n["bfi"]]), lib_ptr(xg), 3 * d.D)
-                lib.call("lvsr_gather_rows", st, lib_ptr(p[n["Wfg"]]), 2 * d.D, lib_ptr(labels_flat), nrows, d.FB, 2 * d.D,
-                         lib_ptr(p[n["bfg"]]), lib_ptr(xg[:, d.D:]), 3 * d.D)
+    def _layer_xgs(self, blk, rows=slice(None)):
+        """[(parameter names, xg)] of the layers of a block set, as `_feedback_forks` takes them."""
+        return [(n, lay["bufs"]["xg"][rows]) for n, lay in zip(self.nl, blk["layers"])]
 
     def _step_blocks(self, pk, A, PA, Am, L, B, tag, att_bufs, ym, att_phases, step0, broadcast, step_dev=None, groups=0, group_Tp=None):
         """Buffers and argument blocks of `L` label steps: att_bufs = the attention block's slots (S (L+1,B,n*D), W, pos, WA,
@@ -175,16 +142,15 @@ class StackedSequenceGenerator(SequenceGenerator):
         D = d.D
         layers = []
         for l in range(d.n_dec):
-            t = "%s.l%d" % (tag, l)
-            WA_l = att_bufs["WA"] if l == 0 else ws.get(t + ".WA", (L, B, self._E(l)))
+            t = "%s.l%d." % (tag, l)
+            WA_l = att_bufs["WA"] if l == 0 else ws.get(t + "WA", (L, B, self._E(l)))
             # the layer's states are a column block of the attention block's (L+1, B, n*D) slots: S_ld = n*D in its argument block
-            bufs = dict(xg=ws.get(t + ".xg", (L * B, 3 * D)), ymask=ym, S=att_bufs["S"][:, :, l * D:(l + 1) * D], WA=WA_l,
-                        U=ws.get(t + ".U", (L, B, D)), R=ws.get(t + ".R", (L, B, D)), C=ws.get(t + ".C", (L, B, D)),
-                        RH=ws.get(t + ".RH", (L, B, D)), sg=ws.get(t + ".sg", (B, 2 * D)), xin=ws.get(t + ".xin", (B, D)))
+            bufs = self._attdec_bufs(t, "", L, B, att=False, xg=ws.get(t + "xg", (L * B, 3 * D)), ymask=ym,
+                                     S=att_bufs["S"][:, :, l * D:(l + 1) * D], WA=WA_l)
             fields = self._layer_fields(l, pk, A, PA, Am, L, B, bufs, broadcast)
             fields["S_ld"] = d.D_tot
             layers.append(dict(bufs=bufs, fields=fields, args=lib.make("lvsr_attdec_args", **fields)))
-        fields = self._att_fields(pk, A, PA, Am, L, B, att_bufs, att_phases, step0, broadcast, groups=groups, group_Tp=group_Tp)
+        fields = self._attdec_fields(pk, A, PA, Am, L, B, att_bufs, att_phases, step0, broadcast, groups=groups, group_Tp=group_Tp)
         extra = {} if step_dev is None else dict(step_dev=step_dev)
         return dict(L=L, att=dict(bufs=att_bufs, fields=fields, args=lib.make("lvsr_attdec_args", **dict(fields, **extra))),
                     layers=layers)
@@ -214,16 +180,11 @@ class StackedSequenceGenerator(SequenceGenerator):
     # ---- teacher-forced pass ---------------------------------------------------------------------------------------------
     def _forward_recurrent(self, pk, A, PA, Am, labels, ym, L, B, Tp):
         d, lib, ws = self.d, self.lib, self.ws
-        Kc = max(d.K, 1)
-        S = ws.get("gen.S", (L + 1, B, d.D_tot))
-        W = ws.get("gen.W", (L + 1, B, Tp))
-        att_bufs = dict(S=S, W=W, pos=ws.get("gen.pos", (L + 1, B)) if (d.conv and self._prior()[0] != 0) else None,
-                        WA=ws.get("gen.WA", (L, B, d.E)), EN=ws.get("gen.EN", (L, B, Tp)), ZB=ws.get("gen.ZB", (L, B)),
-                        sW=ws.get("gen.sW", (L, B, d.M)), CV=ws.get("gen.CV", (L, B, Kc, Tp)) if d.conv else None,
-                        ep=ws.get("gen.ep", (B, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
+        att_bufs = self._attdec_bufs("gen.", "", L, B, Tp, gru=False, ZB=True)
+        S, W = att_bufs["S"], att_bufs["W"]
         blk = self._step_blocks(pk, A, PA, Am, L, B, "gen", att_bufs, ym, att_phases=1, step0=0, broadcast=False)
         fb = ws.get("gen.fb", (L * B, d.FB)) if d.embed else None
-        self._feedback_forks(labels.view(-1), L * B, [lay["bufs"]["xg"] for lay in blk["layers"]], fb)
+        self._feedback_forks(labels.view(-1), L * B, self._layer_xgs(blk), fb)
         S[0].copy_(self._initial_state().unsqueeze(0).expand(B, d.D_tot))       # initial_state of every layer, tiled
         W[0].zero_()
         if d.conv:
@@ -249,32 +210,25 @@ class StackedSequenceGenerator(SequenceGenerator):
         D, E = d.D, d.E
         l0, l1 = blk["layers"]
         n0, n1 = self.nl
-        kind, pp = self._prior()
-        f = dict(Tp=Tp, B=B, L=L, E=E, D=D, M=d.M, K=d.K, c=d.c, prior_type=kind, step0=0, phases=3, p0=pp[0], p1=pp[1], p2=pp[2],
-                 p3=pp[3], A=A, PA=PA, Am=Am, w_e=p[self.n["we"]], normalizer=NORMALIZER_KIND[d.normalizer],
-                 e_bias=p[self.n["eb"]] if d.energy_bias else None, filters=p[self.n["filters"]] if d.conv else None,
-                 handler=p[self.n["handler"]] if d.conv else None, S_ld=d.D_tot)
-        f.update(self._strides(B, False))
-        f.update({k: v for k, v in att_bufs.items() if k != "ep"})
-        f.update(xg=l0["bufs"]["xg"], ymask=l0["bufs"]["ymask"], U=l0["bufs"]["U"], R=l0["bufs"]["R"], C=l0["bufs"]["C"], RH=l0["bufs"]["RH"])
+        # the attention over layer 0's column block (S_ld) with layer 0's GRU slots: the one-layer block of the first cluster
+        f = self._att_fields(A, PA, Am, L, B, D, {k: v for k, v in att_bufs.items() if k != "ep"}, phases=3, step0=0, broadcast=False)
+        f.update(S_ld=d.D_tot, **{k: l0["bufs"][k] for k in ("xg", "ymask", "U", "R", "C", "RH")})
         args = lib.make("lvsr_attdec_args", **f)
-        nbytes = int(lib._lvsr_attdec_stack2_persist_ws_bytes(ctypes.byref(args)))
-        if nbytes == 0:
+        sync = self._persist_sync("lvsr_attdec_stack2_persist_ws_bytes", args, "gen.sync")
+        if sync is None:
             if self.use_persistent_stack:
                 raise ValueError("persistent stacked decoder requested but the configuration is outside the kernel's limits")
             return None
-        sync = ws.get("gen.sync", ((nbytes + 3) // 4,), torch.int32)
-        cats = self._cats()
         wd0, wd1 = ws.get("gen.Wd_cat0", (E, 3 * D)), ws.get("gen.Wd_cat1", (E + D, 3 * D))
         AW0, AW1 = ws.get("gen.AW0", (Tp * B, 3 * D)), ws.get("gen.AW1", (Tp * B, 3 * D))
         A2 = A.view(Tp * B, E)
         lib.sgemm(A2, wd0, AW0)
         lib.sgemm(A2, wd1[:E], AW1)
-        plain = lib.make("lvsr_attdec_plain", Ws=p[n0["Ws"]], Whg=p[n0["Whg"]], Whh=p[n0["Whh"]], AW=AW0, AW_ld=0)
+        plain = self._plain(n0, AW0, 0)
         b1 = l1["bufs"]
         st2 = lib.make("lvsr_attdec_stack2", Whg1=p[n1["Whg"]], Whh1=p[n1["Whh"]], Ws1=p[n1["Ws"]], F1=wd1[E:], AW1=AW1, xg1=b1["xg"],
                        U1=b1["U"], R1=b1["R"], C1=b1["C"], RH1=b1["RH"], F1_ld=0, AW1_ld=0)
-        lib.call("lvsr_attdec_fwd_persistent_stack2", stream, ctypes.byref(args), ctypes.byref(plain), ctypes.byref(st2), lib_ptr(sync), 0)
+        lib.call("lvsr_attdec_fwd_persistent_stack2", stream, ctypes.byref(args), ctypes.byref(plain), ctypes.byref(st2), ptr(sync), 0)
         lib.call("lvsr_attdec_glimpses", stream, ctypes.byref(args))
         WA1 = b1["WA"].view(L * B, E + D)
         lib.copy_many([(att_bufs["WA"].view(L * B, E), WA1[:, :E]), (att_bufs["S"][1:].reshape(L * B, d.D_tot)[:, :D], WA1[:, E:])])
@@ -317,29 +271,22 @@ class StackedSequenceGenerator(SequenceGenerator):
         stream = lib.stream_for(ds)
         st2 = sv.get("stack2")
         psync = None
-        if st2 is not None and self.use_persistent_stack is not False:
+        if st2 is not None and self.use_persistent_stack is not False:      # the forward pass has decided about the emulator
             fargs = lib.make("lvsr_attdec_args", **st2["fields"])
-            nbytes = int(lib._lvsr_attdec_stack2_bwd_persist_ws_bytes(ctypes.byref(fargs)))
-            if nbytes > 0:
-                psync = ws.get("gen.sync_bwd", ((nbytes + 3) // 4,), torch.int32)
+            psync = self._persist_sync("lvsr_attdec_stack2_bwd_persist_ws_bytes", fargs, "gen.sync_bwd", emulated=False)
         if psync is not None:
             # the whole reverse walk of both layers as one persistent launch (csrc/decoder_persist_bwd.hip, two clusters per utterance)
             n0, n1 = self.nl
-            P = int(lib._lvsr_attdec_stack2_bwd_persist_clusters(ctypes.byref(fargs)))
-            accH = ws.get("gen.accH_p", (B * P, Kc * d.M))
-            accWe = ws.get("gen.accWe_p", (B * P, d.M))
-            accEb = ws.get("gen.accEb_p", (B * P, 1))
-            QR = ws.get("gen.QR", (L, B, Tp))
-            lib.call("lvsr_sgemm_batched", stream, 0, 1, L, Tp, E, 1.0, lib_ptr(dWA_r), B * E, E,
-                     lib_ptr(sv["A"]), B * E, E, 0.0, lib_ptr(QR), B * Tp, Tp, B)
+            accH, accWe, accEb = self._cluster_partials("lvsr_attdec_stack2_bwd_persist_clusters", fargs, B)
+            QR = self._QR(sv, dWA_r)
             bw = lib.make("lvsr_attdec_bwd_args", dS_r=dS_r, DXG=bws[0]["DXG"], DSW=DSW, DCV=DCV, dPA=dPA, accH=accH, accWe=accWe,
                           accEb=accEb, ds=ds, AW=st2["AW0"], QR=QR, AW_ld=0, ds_ld=DT)
             bw.f = fargs
-            plain = lib.make("lvsr_attdec_plain", Ws=p[n0["Ws"]], Whg=p[n0["Whg"]], Whh=p[n0["Whh"]], AW=st2["AW0"], AW_ld=0)
+            plain = self._plain(n0, st2["AW0"], 0)
             b1 = layers[1]["bufs"]
             s2 = lib.make("lvsr_attdec_stack2", Whg1=p[n1["Whg"]], Whh1=p[n1["Whh"]], Ws1=p[n1["Ws"]], F1=st2["wd1"][E:], AW1=st2["AW1"],
                           xg1=b1["xg"], U1=b1["U"], R1=b1["R"], C1=b1["C"], RH1=b1["RH"], F1_ld=0, AW1_ld=0, DXG1=bws[1]["DXG"])
-            lib.call("lvsr_attdec_bwd_persistent_stack2", stream, ctypes.byref(bw), ctypes.byref(plain), ctypes.byref(s2), lib_ptr(psync))
+            lib.call("lvsr_attdec_bwd_persistent_stack2", stream, ctypes.byref(bw), ctypes.byref(plain), ctypes.byref(s2), ptr(psync))
             # total gradient wrt the glimpses (the kernel does not form it): the readout's share + both layers' distribution inputs
             DWA2 = DWA.view(nrows, E)
             lib.copy_many([(dWA_r.view(nrows, E), DWA2)])
@@ -361,8 +308,6 @@ class StackedSequenceGenerator(SequenceGenerator):
             lib.call("lvsr_attdec_bwd", stream, ctypes.byref(bw_att), 0)
         # ---- weight gradients as batched GEMMs over all labels
         Scat2 = att["bufs"]["S"][:L].view(nrows, DT)
-        labels_flat = sv["labels"].view(-1)
-        fb = sv["fb"]
         dfb = ws.get("gen.dfb", (nrows, d.FB)) if d.embed else None
         for l, (n, lay, bwl) in enumerate(zip(self.nl, layers, bws)):
             dpc, dg = bwl["DXG"][:, :D], bwl["DXG"][:, D:]
@@ -379,19 +324,7 @@ class StackedSequenceGenerator(SequenceGenerator):
             colsum(bwl["ds"], g[n["h0"]])
             colsum(dpc, g[n["bfi"]])
             colsum(dg, g[n["bfg"]])
-            if d.embed:
-                wgrad(fb, dpc, g[n["Wfi"]])
-                wgrad(fb, dg, g[n["Wfg"]])
-                lib.sgemm(dpc, p[n["Wfi"]], dfb, transB=True, beta=0.0 if l == 0 else 1.0)
-                lib.sgemm(dg, p[n["Wfg"]], dfb, transB=True, beta=1.0)
-            else:
-                lib.call("lvsr_scatter_add_rows", stream, lib_ptr(dpc), 3 * D, lib_ptr(labels_flat), nrows, d.FB, D,
-                         lib_ptr(g[n["Wfi"]]), D, 0.0)
-                lib.call("lvsr_scatter_add_rows", stream, lib_ptr(dg), 3 * D, lib_ptr(labels_flat), nrows, d.FB, 2 * D,
-                         lib_ptr(g[n["Wfg"]]), 2 * D, 0.0)
-        if d.embed:
-            lib.call("lvsr_scatter_add_rows", stream, lib_ptr(dfb), d.FB, lib_ptr(labels_flat), nrows, d.V + 1, d.FB,
-                     lib_ptr(g[self.n["table"]]), d.FB, 0.0)
+            self._feedback_forks_backward(l, n, sv, bwl["DXG"], dfb, wgrad)
         return dict(accH=accH, accWe=accWe, accEb=accEb, DCV=DCV, dPA=dPA, DWA=DWA,
                     fwd_args=lib.make("lvsr_attdec_args", **att["fields"]))
 
@@ -405,8 +338,7 @@ class StackedSequenceGenerator(SequenceGenerator):
     def _beam_step_run(self, st):
         lib, blk = self.lib, st["stepB"]
         S = blk["att"]["bufs"]["S"]
-        layers = blk["layers"]
-        self._feedback_forks(st["chars"], st["rows"], [lay["bufs"]["xg"] for lay in layers], st["fb"])
+        self._feedback_forks(st["chars"], st["rows"], self._layer_xgs(blk), st["fb"])
         self._run_step(blk, 0, lib.stream_for(S))
 
     # ---- free-running generation -----------------------------------------------------------------------------------------
@@ -424,14 +356,9 @@ class StackedSequenceGenerator(SequenceGenerator):
         A, Am = attended.contiguous(), attended_mask.contiguous()
         PA = self.preprocess(A)
         u = self._uniforms((N, B), uniforms, seed, A.device)
-        Kc = max(d.K, 1)
-        pos_needed = d.conv and self._prior()[0] != 0
-        S = ws.get("sg.S", (N + 1, B, d.D_tot))
-        W = ws.get("sg.W", (N + 1, B, Tp))
-        att_bufs = dict(S=S, W=W, pos=ws.get("sg.pos", (N + 1, B)) if pos_needed else None, WA=ws.get("sg.WA", (N, B, d.E)),
-                        EN=ws.get("sg.EN", (N, B, Tp)), ZB=None, sW=ws.get("sg.sW", (N, B, d.M)),
-                        CV=ws.get("sg.CV", (N, B, Kc, Tp)) if d.conv else None,
-                        ep=ws.get("sg.ep", (B, (d.M + ATT_MS - 1) // ATT_MS, Tp)))
+        pos_needed = self._pos_needed()
+        att_bufs = self._attdec_bufs("sg.", "", N, B, Tp, gru=False)
+        S, W = att_bufs["S"], att_bufs["W"]
         blk = self._step_blocks(pk, A, PA, Am, N, B, "sg", att_bufs, None, att_phases=1 | (4 if pos_needed else 0), step0=0,
                                 broadcast=False)
         first = self.initial_states(B, attended=A)
@@ -447,14 +374,7 @@ class StackedSequenceGenerator(SequenceGenerator):
             self._run_attention(blk, t, st)
             ra = self._readout_step_args(S[t], att_bufs["WA"][t], B, uniforms=u[t], outputs=outputs[t], costs=costs[t])
             lib.call("lvsr_readout_step", st, ctypes.byref(ra))
-            self._feedback_forks(outputs[t], B, [lay["bufs"]["xg"][t * B:(t + 1) * B] for lay in blk["layers"]], fb)
+            self._feedback_forks(outputs[t], B, self._layer_xgs(blk, slice(t * B, (t + 1) * B)), fb)
             self._run_layers(blk, t, st)
         return dict(states=S[1:], outputs=outputs, weighted_averages=att_bufs["WA"], weights=W[1:], energies=att_bufs["EN"],
                     costs=costs)
-
-    # ---- not built for a stack ----------------------------------------------------------------------------------------------
-    def generation_initial_states(self, n=1):
-        raise NotImplementedError("the step-wise generation helpers are one-layer only; dec_stack > 1 decodes through beam_begin / "
-                                  "beam_step")
-
-    generation_logprobs = generation_next_states = _gen_run = generation_initial_states
