@@ -324,6 +324,30 @@ __global__ __launch_bounds__(256) void readout_step_kernel(lvsr_readout_step_arg
     const int lane = tid & 63, V = a.V;
     const bool w0 = tid < 64;
     const float* l = a.lm_add ? a.lm_add + (size_t)r * V : nullptr;
+    if (a.emitter == 1) {
+        // RewardRegressionEmitter (lvsr/bricks/__init__.py:183-192): costs = -readouts, emit = argmax (the first maximal class, as
+        // numpy's), cost of the emitted class = +readouts[class]
+        if (w0) {
+            float bv = -3.0e38f;
+            int bi = V;
+            for (int v = lane; v < V; v += 64) {
+                const float x = logits[v];
+                if (a.neglogp) a.neglogp[(size_t)r * V + v] = -x;
+                if (bi == V || x > bv) { bv = x; bi = v; }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const float ov = __shfl_xor(bv, o, 64);
+                const int oi = __shfl_xor(bi, o, 64);
+                if (oi < V && (bi == V || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+            }
+            if (a.outputs && lane == 0) {
+                a.outputs[r] = bi;
+                if (a.costs) a.costs[r] = bv;
+            }
+        }
+        return;
+    }
     if (w0) {
         float lse_a = 0.f, lse_l = 0.f, lse_t = 0.f, mx0 = 0.f;
         if (!l) {
@@ -419,6 +443,8 @@ int lvsr_readout_step(void* stream, const lvsr_readout_step_args* args) {
     LVSR_REQUIRE(a.Wout != nullptr || a.P == a.V, "lvsr_readout_step: without a post-merge layer the merge width must be V");
     LVSR_REQUIRE(a.act >= 0 && a.act <= 3 && (a.act != 1 || a.P % 2 == 0), "lvsr_readout_step: bad activation");
     LVSR_REQUIRE(!a.uniforms || a.outputs, "lvsr_readout_step: emit needs an output buffer");
+    LVSR_REQUIRE(a.emitter == 0 || (a.emitter == 1 && !a.lm_add),
+                 "lvsr_readout_step: emitter must be 0 (softmax) or 1 (reward regression, without a language model)");
     LVSR_REQUIRE(a.n_hidden >= 0 && a.n_hidden <= 3 && (a.n_hidden == 0 || (a.Wout && (a.act == 2 || a.act == 3))),
                  "lvsr_readout_step: further post-merge layers need a one-piece activation and an output layer");
     for (int h = 0; h < a.n_hidden; ++h)

@@ -5,7 +5,9 @@
 `SoftmaxEmitter` (:751-800), as wired by `SpeechRecognizer.__init__` (lvsr/bricks/recognizer.py:250-343).
 
 `cost_matrix(outputs, mask, attended=, attended_mask=)` keeps the reference signature
-(sequence_generators.py:317-326); `backward()` is the counterpart of theano.grad through it.  All arithmetic
+(sequence_generators.py:317-326); `backward()` is the counterpart of theano.grad through it.  With the mse_gain / mse_reward
+criteria the emitter is `RewardRegressionEmitter` (lvsr/bricks/__init__.py:119-202): `outputs` is then the prediction that drives
+the decoder and `groundtruth=` what its rewards are measured against.  All arithmetic
 is in the C-ABI library; torch only owns buffers/views.
 """
 import ctypes
@@ -41,6 +43,10 @@ class SequenceGenerator(object):
         self._packs = None
         self._pack_cache = {}
         self._saved = None
+        # the emitter (recognizer.py:285-297): SoftmaxEmitter, or RewardRegressionEmitter for the mse_gain / mse_reward criteria
+        self.criterion = dims.cfg["criterion"]
+        self.mse = self.criterion != "log_likelihood"
+        self.min_reward = float(dims.cfg["min_reward"])
         g = "/recognizer/generator"
         att = g + "/att_trans/" + ("conv_att" if dims.conv else "cont_att")
         self.n = dict(
@@ -346,10 +352,32 @@ class SequenceGenerator(object):
                                    "the last check are invalid")
 
     # ---- teacher-forced cost ---------------------------------------------------------------------
-    def cost_matrix(self, outputs, mask=None, attended=None, attended_mask=None, save_for_backward=True):
+    def _check_emitter(self):
+        if self.mse and self.language_model is not None:
+            raise NotImplementedError("criterion %s with a language model is not built" % self.criterion)
+
+    def reward_matrices(self, groundtruth, prediction, want_mask=False):
+        """RewardOp (lvsr/ops.py:236-294) on the device: groundtruth (Lg,B), prediction (Lp,B) int64 -> dict(rewards, gains (Lp,B,V),
+        mask (Lp,B): the prediction up to and including its first EOS, lvsr/main.py:254-259; only with `want_mask`).  Groundtruth
+        columns must end in EOS (a column without one is used whole; the reference raises there)."""
+        d, lib, ws = self.d, self.lib, self.ws
+        Lp, B = int(prediction.shape[0]), int(prediction.shape[1])
+        gt, pred = groundtruth.contiguous(), prediction.contiguous()
+        out = dict(rewards=ws.get("gen.reward_matrix", (Lp, B, d.V)), gains=ws.get("gen.gain_matrix", (Lp, B, d.V)),
+                   mask=ws.get("gen.prediction_mask", (Lp, B)) if want_mask else None)
+        lib.call("lvsr_reward_gain", lib.stream_for(out["rewards"]), ptr(gt), int(gt.shape[0]), ptr(pred), Lp, B, int(d.cfg["eos_label"]),
+                 d.V, ptr(out["rewards"]), ptr(out["gains"]), ptr(out["mask"]))
+        return out
+
+    def cost_matrix(self, outputs, mask=None, attended=None, attended_mask=None, save_for_backward=True, groundtruth=None,
+                    rewards=None):
         """outputs (L,B) int64 labels, mask (L,B) or None, attended (T',B,E), attended_mask (T',B) -> costs (L,B).
         Also keeps `self.last` = dict(weights, energies, states, weighted_averages) (the auxiliary variables
-        `SpeechRecognizer.analyze` extracts, recognizer.py:452-494)."""
+        `SpeechRecognizer.analyze` extracts, recognizer.py:452-494).
+        mse criteria: `outputs` / `mask` are the prediction, `groundtruth` (Lg,B; default: `outputs`, the placeholder the reference's
+        get_cost_graph swaps, recognizer.py:437-449) is what the rewards are measured against; `rewards`: the result of
+        `reward_matrices` when the caller has run it already.  `last` also holds readouts, gain_matrix and reward_matrix."""
+        self._check_emitter()
         d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
         L, B = int(outputs.shape[0]), int(outputs.shape[1])
         Tp = int(attended.shape[0])
@@ -366,8 +394,14 @@ class SequenceGenerator(object):
         R1, R2, logits = self._readout(S2, WA2, L * B, "")
         cost = ws.get("gen.cost", (L, B))
         dlogits = ws.get("gen.dlogits", (L * B, d.V))
-        lib.call("lvsr_softmax_nll", lib.stream_for(cost), ptr(logits), d.V, ptr(labels), ptr(ym), L * B, d.V,
-                 ptr(cost), ptr(dlogits), d.V, 1.0, None, 0)
+        if self.mse:
+            # RewardRegressionEmitter.cost (lvsr/bricks/__init__.py:134-183) in place of the softmax cross-entropy
+            rw = rewards if rewards is not None else self.reward_matrices(labels if groundtruth is None else groundtruth, labels)
+            lib.call("lvsr_reward_mse", lib.stream_for(cost), int(self.criterion == "mse_reward"), ptr(logits), d.V, ptr(rw["gains"]),
+                     ptr(rw["rewards"]), ptr(labels), ptr(ym), L, B, d.V, self.min_reward, ptr(cost), ptr(dlogits), d.V)
+        else:
+            lib.call("lvsr_softmax_nll", lib.stream_for(cost), ptr(logits), d.V, ptr(labels), ptr(ym), L * B, d.V,
+                     ptr(cost), ptr(dlogits), d.V, 1.0, None, 0)
         lm = self.language_model
         self._cost_has_lm = lm is not None
         if lm is not None:
@@ -381,6 +415,8 @@ class SequenceGenerator(object):
             lib.call("lvsr_select_cost", lib.stream_for(cost), ptr(fused), d.V, ptr(labels), ptr(ym), L * B, d.V, -1.0,
                      ptr(cost))
         self.last = dict(weights=W[1:], energies=bufs["EN"], states=S[:L], weighted_averages=WA)
+        if self.mse:
+            self.last.update(readouts=logits.view(L, B, d.V), gain_matrix=rw["gains"], reward_matrix=rw["rewards"])
         if save_for_backward:
             self._saved = dict(L=L, B=B, Tp=Tp, A=A, Am=Am, PA=PA, labels=labels, ym=ym, bufs=bufs,
                                R1=R1, R2=R2, dlogits=dlogits, pk=pk, pm_acts=list(self._pm_acts))
@@ -610,7 +646,7 @@ class SequenceGenerator(object):
         B = int(batch_size)
         Tp = int(attended.shape[0]) if attended is not None else 0
         out = dict(states=h0.unsqueeze(0).expand(B, self._state_width()).clone(),
-                   outputs=torch.full((B,), d.V, dtype=torch.int64, device=dev),
+                   outputs=torch.full((B,), 0 if self.mse else d.V, dtype=torch.int64, device=dev),      # RewardRegressionEmitter: zeros
                    weighted_averages=torch.zeros(B, d.E, device=dev), weights=torch.zeros(B, Tp, device=dev))
         if d.conv:
             if Tp:
@@ -654,6 +690,7 @@ class SequenceGenerator(object):
         draws (see `emit`).  -> dict(states (n,B,D), outputs (n,B) int64, weighted_averages (n,B,E), weights (n,B,T'),
         energies (n,B,T'), costs (n,B))."""
         d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
+        self._check_emitter()
         if self.language_model is not None:
             # With a language model the reference's emitter is LMEmitter, whose `emit` returns zeros "that should never be used"
             # (lvsr/bricks/language_models.py:160-163): free-running generation is not a path of the reference there — beam search
@@ -667,13 +704,16 @@ class SequenceGenerator(object):
         A, Am = attended.contiguous(), attended_mask.contiguous()
         PA = self.preprocess(A)
         dev = A.device
-        u = self._uniforms((N, B), uniforms, seed, dev)
+        # RewardRegressionEmitter.emit is the argmax (lvsr/bricks/__init__.py:186-188): no random numbers
+        u = None if self.mse else self._uniforms((N, B), uniforms, seed, dev)
         pos_needed = self._pos_needed()
         S = ws.get("sg.S", (N + 1, B, d.D))
         W = ws.get("sg.W", (N + 1, B, Tp))
-        first = self.initial_states(B, attended=A)
-        S[0].copy_(first["states"])
-        W[0].copy_(first["weights"])
+        # `initial_states` written in place (nothing is allocated: greedy exploration runs this inside a captured training step)
+        S[0].copy_(self._initial_state().unsqueeze(0).expand(B, d.D))
+        W[0].zero_()
+        if d.conv:
+            W[0, :, 0] = 1.0
         full = self._attdec_bufs("sg.", "", N, B, Tp, S=S, W=W, xg=ws.get("sg.xg", (N, B, 3 * d.D)), ymask=None)
         outputs = ws.get("sg.outputs", (N, B), torch.int64)
         costs = ws.get("sg.costs", (N, B))
@@ -687,7 +727,7 @@ class SequenceGenerator(object):
             skip = 4 if pos_needed else 0
             fa = self._attdec_fields(pk, A, PA, Am, 1, B, bufs, phases=1 | skip, step0=t, broadcast=False)
             lib.call("lvsr_attdec_fwd", st, ctypes.byref(lib.make("lvsr_attdec_args", **fa)), 0)
-            ra = self._readout_step_args(S[t], full["WA"][t], B, uniforms=u[t], outputs=outputs[t], costs=costs[t])
+            ra = self._readout_step_args(S[t], full["WA"][t], B, uniforms=None if u is None else u[t], outputs=outputs[t], costs=costs[t])
             lib.call("lvsr_readout_step", st, ctypes.byref(ra))
             self._feedback_forks(outputs[t], B, [(n, full["xg"][t])], fb)
             fg = self._attdec_fields(pk, A, PA, Am, 1, B, bufs, phases=2, step0=t, broadcast=False)
@@ -702,6 +742,7 @@ class SequenceGenerator(object):
         After `init_generation` on a batch of N utterances: N searches side by side (`max_length` = one limit per utterance),
         search g in rows [g K, g K + K) of every state buffer and block g of the bookkeeping buffers (lvsr_beam_args.groups)."""
         d, p, n_, lib, ws, g = self.d, self.store.p, self.n, self.lib, self.ws, self._gen
+        self._check_emitter()
         Tp, dev = g["Tp"], g["A"].device
         lm = self.language_model
         on_dev_lm = lm is not None and getattr(lm, "on_device", False)
@@ -828,7 +869,7 @@ class SequenceGenerator(object):
         lm_key = None if lm is None else (float(lm.lm_weight), float(lm.am_beta), tuple(bool(v) for v in lm.norm), float(getattr(lm, "no_transition_cost", 0.0)))
         lm_ptrs = () if not on_dev_lm else tuple(sorted((k, t.data_ptr()) for k, t in lm._dev.items())) + (lm._err.data_ptr(),)
         st["key"] = ("beam_step", K_one, G, Tp, int(max_length), stop_on, int(bool(ignore_first_eol)), int(eol), float(char_discount),
-                     float(round_to_inf), lm is not None, on_dev_lm, lm_key, R1 is not None)
+                     float(round_to_inf), lm is not None, on_dev_lm, lm_key, R1 is not None, self.criterion)
         st["volatile"] = (g["A"].data_ptr(), g["PA"].data_ptr(), g["Am"].data_ptr(), ws.generation, id(pk), self.store.version, lm_ptrs)
         self._beam = st
         return st
@@ -846,7 +887,7 @@ class SequenceGenerator(object):
             am_beta=lm.am_beta if lm_add is not None else 1.0, lm_weight=lm.lm_weight if lm_add is not None else 0.0,
             norm_am=int(lm.norm[0]) if lm_add is not None else 1, norm_lm=int(lm.norm[1]) if lm_add is not None else 0,
             norm_tot=int(lm.norm[2]) if lm_add is not None else 0, neglogp=neglogp, logits=logits, uniforms=uniforms,
-            R1=R1, ldr1=0 if R1 is None else int(R1.stride(0)),
+            R1=R1, ldr1=0 if R1 is None else int(R1.stride(0)), emitter=int(self.mse),
             outputs=outputs, costs=costs, n_hidden=len(self.pm_hidden), Wh=[p[w] for w, _, _ in self.pm_hidden],
             bh=[p[b] for _, b, _ in self.pm_hidden], dimh=[w for _, _, w in self.pm_hidden])
 

@@ -346,6 +346,7 @@ class StackedSequenceGenerator(SequenceGenerator):
         """BaseSequenceGenerator.generate (sequence_generators.py:328-377) with the stacked transition; `states` comes back with the
         layers side by side, (n, B, dec_stack * D)."""
         d, lib, ws = self.d, self.lib, self.ws
+        self._check_emitter()
         if self.language_model is not None:
             raise NotImplementedError("generate() with a language model: the reference's LMEmitter.emit returns zeros (not a "
                                       "sampling path); use beam_search, or cost / analyze for teacher-forced costs")
@@ -355,15 +356,17 @@ class StackedSequenceGenerator(SequenceGenerator):
         pk = self._packed()
         A, Am = attended.contiguous(), attended_mask.contiguous()
         PA = self.preprocess(A)
-        u = self._uniforms((N, B), uniforms, seed, A.device)
+        u = None if self.mse else self._uniforms((N, B), uniforms, seed, A.device)        # the mse emitter is the argmax
         pos_needed = self._pos_needed()
         att_bufs = self._attdec_bufs("sg.", "", N, B, Tp, gru=False)
         S, W = att_bufs["S"], att_bufs["W"]
         blk = self._step_blocks(pk, A, PA, Am, N, B, "sg", att_bufs, None, att_phases=1 | (4 if pos_needed else 0), step0=0,
                                 broadcast=False)
-        first = self.initial_states(B, attended=A)
-        S[0].copy_(first["states"])
-        W[0].copy_(first["weights"])
+        # `initial_states` written in place (nothing is allocated: greedy exploration runs this inside a captured training step)
+        S[0].copy_(self._initial_state().unsqueeze(0).expand(B, d.D_tot))
+        W[0].zero_()
+        if d.conv:
+            W[0, :, 0] = 1.0
         if pos_needed:
             att_bufs["pos"][0].zero_()
         outputs = ws.get("sg.outputs", (N, B), torch.int64)
@@ -372,7 +375,8 @@ class StackedSequenceGenerator(SequenceGenerator):
         st = lib.stream_for(S)
         for t in range(N):
             self._run_attention(blk, t, st)
-            ra = self._readout_step_args(S[t], att_bufs["WA"][t], B, uniforms=u[t], outputs=outputs[t], costs=costs[t])
+            ra = self._readout_step_args(S[t], att_bufs["WA"][t], B, uniforms=None if u is None else u[t], outputs=outputs[t],
+                                         costs=costs[t])
             lib.call("lvsr_readout_step", st, ctypes.byref(ra))
             self._feedback_forks(outputs[t], B, self._layer_xgs(blk, slice(t * B, (t + 1) * B)), fb)
             self._run_layers(blk, t, st)

@@ -162,28 +162,48 @@ class SpeechRecognizer(object):
         self.store.set_values(values)
 
     # ---- training cost (recognizer.py:375-390) -------------------------------------------------------
-    def cost(self, recordings=None, inputs_mask=None, labels=None, labels_mask=None, save_for_backward=True, **kw):
+    def cost(self, recordings=None, inputs_mask=None, labels=None, labels_mask=None, save_for_backward=True, prediction=None,
+             prediction_mask=None, **kw):
         """-> cost matrix (L,B) on the device.  `recordings` (T,B,F), `inputs_mask` (T,B) or None,
-        `labels` (L,B) int64, `labels_mask` (L,B) or None."""
+        `labels` (L,B) int64, `labels_mask` (L,B) or None.
+        `prediction` (Lp,B) int64 / `prediction_mask` (get_cost_graph, recognizer.py:423-450): the prediction drives the decoder and
+        is what the cost is taken on -> (Lp,B); the labels are the groundtruth its rewards are measured against (mse criteria)."""
         if "recordings_mask" in kw:
             inputs_mask = kw.pop("recordings_mask")
         if kw:
             raise TypeError("unknown inputs: %s" % sorted(kw))
         with self._on_stream():
             x, xm, y, ym = self._stage(recordings, inputs_mask, labels, labels_mask)
-            cm = self._forward(x, xm, y, ym, save_for_backward)
-        return cm
+            if prediction is None:
+                return self._forward(x, xm, y, ym, save_for_backward)
+            pr, pm = self._t(prediction, torch.int64, "prediction"), self._t(prediction_mask, torch.float32, "prediction_mask")
+            return self._forward(x, xm, pr, pm, save_for_backward, groundtruth=y)
 
     def _stage(self, recordings, inputs_mask, labels, labels_mask):
         return (self._t(recordings, torch.float32, "recordings"), self._t(inputs_mask, torch.float32, "recordings_mask"),
                 self._t(labels, torch.int64, "labels"), self._t(labels_mask, torch.float32, "labels_mask"))
 
-    def _forward(self, x, xm, y, ym, save_for_backward=True):
+    def _forward(self, x, xm, y, ym, save_for_backward=True, groundtruth=None):
         encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, save_for_backward), xm,
                                                    save_for_backward=save_for_backward)
         self.encoded, self.encoded_mask = encoded, encoded_mask
         return self.generator.cost_matrix(y, ym, attended=encoded, attended_mask=encoded_mask,
-                                          save_for_backward=save_for_backward)
+                                          save_for_backward=save_for_backward, groundtruth=groundtruth)
+
+    LENGTH_EXPAND = 10          # greedy exploration generates this many labels more than the groundtruth has (lvsr/main.py:251)
+
+    def _forward_greedy(self, x, xm, y):
+        """The forward pass of a training step with greedy exploration (add_exploration, lvsr/main.py:245-283): encode once, let the
+        argmax emitter generate L + 10 labels, measure them against the groundtruth `y` (reward / gain matrices and the mask of the
+        prediction up to its first EOS, on the device), then the teacher-forced pass on the prediction.  No host synchronisation.
+        -> cost matrix (L + 10, B)."""
+        gen = self.generator
+        encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, True), xm, save_for_backward=True)
+        self.encoded, self.encoded_mask = encoded, encoded_mask
+        prediction = gen.generate(n_steps=int(y.shape[0]) + self.LENGTH_EXPAND, attended=encoded, attended_mask=encoded_mask)["outputs"]
+        rw = gen.reward_matrices(y, prediction, want_mask=True)
+        self.prediction, self.prediction_mask = prediction, rw["mask"]
+        return gen.cost_matrix(prediction, rw["mask"], attended=encoded, attended_mask=encoded_mask, rewards=rw)
 
     # ---- free-running generation (recognizer.py:393-406, 535-547) ------------------------------------------------------
     def generate(self, n_steps=None, inputs_mask=None, recordings=None, uniforms=None, seed=None, **kw):
@@ -248,7 +268,7 @@ class SpeechRecognizer(object):
         assert all(k.startswith("/recognizer/generator") == (o >= first) for k, (o, n) in offs.items()), "decoder parameters are not a tail"
         return first, self.store.flat.numel() - first
 
-    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None, head=None):
+    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None, head=None, exploration=None):
         """One training forward+backward on a batch dict in the reference's layout.
         Returns the cost matrix (L,B) on the device; gradients of its sum are in self.store.grad.
         `tail` (optional callable, described by the hashable `tail_key`) enqueues more work behind the backward pass — the
@@ -257,7 +277,17 @@ class SpeechRecognizer(object):
         the decoder's gradients are final and before the encoder's backward pass is enqueued; the step is then TWO graph regions
         (forward + decoder backward | encoder backward [+ tail]).
         `head` (optional callable, described by `tail_key` as well) enqueues work in front of the forward pass inside the (first)
-        graph region: the noisy weights of adaptive noise."""
+        graph region: the noisy weights of adaptive noise.
+        `exploration`: None / "imitative" = the decoder is driven by the labels; "greedy" (mse criteria, `training.exploration` of the
+        reference, lvsr/main.py:245-283) = by its own argmax prediction of L + 10 labels, generated inside the same graph region
+        (`_forward_greedy`); the cost matrix is then (L + 10, B)."""
+        if exploration not in (None, "imitative", "greedy"):
+            raise ValueError("unknown exploration %r" % (exploration,))
+        greedy = exploration == "greedy"
+        if greedy and not self.generator.mse:
+            raise NotImplementedError("greedy exploration needs an mse criterion (the softmax emitter samples; not built for training)")
+        if greedy and between is not None:
+            raise NotImplementedError("greedy exploration with an overlapped gradient exchange is not built")
         with self._on_stream():
             x, xm, y, ym = self._stage(batch["recordings"], batch.get("recordings_mask"), batch["labels"],
                                        batch.get("labels_mask"))
@@ -288,21 +318,22 @@ class SpeechRecognizer(object):
             def enqueue():
                 if head is not None:
                     head()
-                cm = self._forward(x, xm, y, ym)
+                cm = self._forward_greedy(x, xm, y) if greedy else self._forward(x, xm, y, ym)
                 self.backward()
                 if tail is not None:
                     tail()
                 return cm
-            key = ("train_step",) + shape_key + (tail_key,)
+            key = ("train_step",) + shape_key + (tail_key, "greedy" if greedy else "imitative")
             return self.lib.region(self, key, x, enabled=plain, volatile=volatile).run(enqueue)
 
     # ---- analyze (recognizer.py:452-494) -----------------------------------------------------------
     def analyze(self, inputs, groundtruth, prediction=None):
         """Single utterance: -> [cost (L,), weights (L,T'), energies (L,T')] as numpy arrays."""
         x = numpy.asarray(dict(inputs)["recordings"], dtype=numpy.float32)
-        y = numpy.asarray(prediction if prediction is not None else groundtruth, dtype=numpy.int64)
+        y = numpy.asarray(groundtruth if groundtruth is not None else prediction, dtype=numpy.int64)
+        pr = None if prediction is None else numpy.asarray(prediction, dtype=numpy.int64)[:, None]
         cm = self.cost(recordings=x[:, None, :], inputs_mask=None, labels=y[:, None], labels_mask=None,
-                       save_for_backward=False)
+                       save_for_backward=False, prediction=pr)
         last = self.generator.last
         torch.cuda.synchronize() if self.device.type == "cuda" else None
         return [cm[:, 0].cpu().numpy(), last["weights"][:, 0, :].cpu().numpy(), last["energies"][:, 0, :].cpu().numpy()]
@@ -366,6 +397,8 @@ class SpeechRecognizer(object):
     def set_language_model(self, language_model):
         """Attach (or detach with None) an `lvsr_amd.lm.FSTLanguageModel` for shallow-fusion decoding — the `lm:`
         sub-section of the reference's net config (recognizer.py:322-343)."""
+        if language_model is not None and self.generator.mse:
+            raise NotImplementedError("criterion %s with a language model is not built" % self.generator.criterion)
         if language_model is not None and language_model.out_dim != self.d.V:
             raise ValueError("language model covers %d characters, the recognizer %d" % (language_model.out_dim, self.d.V))
         self.generator.language_model = language_model

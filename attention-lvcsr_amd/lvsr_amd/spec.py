@@ -37,7 +37,11 @@ _DEFAULTS = dict(
     max_decoded_length_scale=1,
     bottom_dims=None,          # SpeechBottom(dims=...): MLP in front of the encoder (recognizer.py:105-126); None/[] = Identity
     bottom_activation="tanh",  # SpeechBottom default Tanh() (recognizer.py:116-117); the configs use Rectifier
+    criterion="log_likelihood",  # 'log_likelihood' (SoftmaxEmitter) | 'mse_gain' | 'mse_reward' (RewardRegressionEmitter, recognizer.py:285-297)
+    min_reward=-1.0,           # criterion.min_reward: the floor of the gains mse_gain regresses on (lvsr/bricks/__init__.py:154)
 )
+
+CRITERIA = ("log_likelihood", "mse_gain", "mse_reward")
 
 DEFAULT_PRIOR = dict(type="expanding", initial_begin=0, initial_end=10000, min_speed=0, max_speed=0)
 
@@ -83,6 +87,9 @@ def normalize_net_config(cfg):
         raise Exception("Unknown energey_normalizer: {}".format(out["energy_normalizer"]))
     if out["attention_type"] == "content" :
         out["energy_normalizer"] = "softmax"          # the Blocks content attention has no such option (recognizer.py:262-265)
+    if out["criterion"] not in CRITERIA:
+        raise ValueError("Unknown criterion {}".format(out["criterion"]))        # recognizer.py:296-297
+    out["min_reward"] = float(out["min_reward"])
     out["bottom_dims"] = [int(v) for v in (out["bottom_dims"] or [])]
     if out["bottom_dims"] and out["bottom_activation"] not in ("rectifier", "tanh", "identity"):
         raise NotImplementedError("bottom activation %r is not built" % out["bottom_activation"])
@@ -348,8 +355,13 @@ def from_reference_kwargs(input_dims=None, input_num_chars=None, eos_label=None,
         tn = _brick_name(trans)
         if tn is not None and tn != "GatedRecurrent":
             raise NotImplementedError("%s=%s: only GatedRecurrent is built" % (which, tn))
-    if criterion is not None and dict(criterion).get("name", "log_likelihood") != "log_likelihood":
-        raise ValueError("Unknown criterion {}".format(criterion["name"]))        # recognizer.py:296-297
+    criterion = dict(criterion or {})
+    criterion_name = criterion.get("name", "log_likelihood")
+    if criterion_name not in CRITERIA:
+        raise ValueError("Unknown criterion {}".format(criterion_name))           # recognizer.py:296-297
+    if criterion_name != "log_likelihood" and lm and dict(lm).get("path"):
+        # the reference builds ShallowFusionReadout around the RewardRegressionEmitter there; that combination is not built
+        raise NotImplementedError("criterion %s with a language model (net.lm) is not built" % criterion_name)
     # `lm` / `character_map` do not change the network: SpeechRecognizer.__init__ builds the fusion model from them
     if not bidir:
         raise NotImplementedError("bidir=False is not built")
@@ -381,7 +393,8 @@ def from_reference_kwargs(input_dims=None, input_num_chars=None, eos_label=None,
                conv_n=conv_n, conv_num_filters=conv_num_filters, prior=prior, energy_normalizer=energy_normalizer,
                post_merge_dims=post_merge_dims, embed_outputs=embed_outputs, dim_output_embedding=dim_output_embedding,
                use_states_for_readout=use_states_for_readout, data_prepend_eos=data_prepend_eos,
-               max_decoded_length_scale=max_decoded_length_scale, bottom_dims=bottom_dims, bottom_activation=bottom_act)
+               max_decoded_length_scale=max_decoded_length_scale, bottom_dims=bottom_dims, bottom_activation=bottom_act,
+               criterion=criterion_name, min_reward=criterion.get("min_reward", -1.0))     # emitter without parameters: same checkpoints
     if post_merge_dims:
         cfg["post_merge_activation"] = _activation_name(post_merge_activation)
     return normalize_net_config(cfg)

@@ -44,13 +44,24 @@ class Trainer(object):
     def __init__(self, recognizer, gradient_threshold=None, rules=("momentum",), scale=0.1, momentum=0.0,
                  decay_rate=0.95, epsilon=1e-8, max_norm=0.0, max_norm_exclude_lookup=False, nonfinite_scaler=0.0,
                  burn_in_steps=0, adaptive_clipping=None, process_group=None, distributed=None, dp_region=True,
-                 overlap_allreduce=False, adaptive_noise=None, num_examples=None):
+                 overlap_allreduce=False, adaptive_noise=None, num_examples=None, exploration="imitative"):
         """Keywords = `training:` / `regularization:` keys of the reference's config (lvsr/main.py:480-519).
         `adaptive_clipping`: None, True or dict(decay_rate=0.998, burnin_period=500) — the AdaptiveClipping extension the
         reference's `train()` always installs on top of `gradient_threshold` (lvsr/main.py:616-619).
         `adaptive_noise`: None, True or dict(model_cost_coefficient=1.0, init_sigma=1e-6, seed=None) — adaptive weight noise
         (lvsr/main.py:425-456, lvsr_amd/weight_noise.py); it needs `num_examples`, the size of the training set.  The step rules then
-        run over theta = [means | log-variances] (max_norm on WEIGHT-role means only) and `store.flat` holds the means between steps."""
+        run over theta = [means | log-variances] (max_norm on WEIGHT-role means only) and `store.flat` holds the means between steps.
+        `exploration` (`training.exploration`, add_exploration, lvsr/main.py:245-283): 'imitative' = the labels drive the decoder;
+        'greedy' (mse criteria) = its own argmax prediction does (SpeechRecognizer.cost_and_gradients); 'mixed' is not built."""
+        if exploration == "mixed":
+            raise NotImplementedError("exploration 'mixed' (a Bernoulli draw per utterance between prediction and labels) is not built")
+        if exploration not in ("imitative", "greedy"):
+            raise ValueError("unknown exploration %r" % (exploration,))          # the reference raises ValueError (lvsr/main.py:280-281)
+        if exploration == "greedy" and not recognizer.generator.mse:
+            raise NotImplementedError("greedy exploration needs an mse criterion (net.criterion.name mse_gain / mse_reward)")
+        if exploration == "greedy" and overlap_allreduce:
+            raise NotImplementedError("greedy exploration with overlap_allreduce is not built")
+        self.exploration = exploration
         from .weight_noise import settings as noise_settings
         noise_conf = noise_settings(adaptive_noise)
         if noise_conf is not None and num_examples is None:
@@ -142,7 +153,7 @@ class Trainer(object):
                    scale=training.get("scale", 0.1), momentum=training.get("momentum", 0.0),
                    decay_rate=training.get("decay_rate", 0.95), epsilon=training.get("epsilon", 1e-8),
                    max_norm=reg.get("max_norm", 0.0) or 0.0, max_norm_exclude_lookup=reg.get("max_norm_exclude_lookup", False),
-                   burn_in_steps=training.get("burn_in_steps", 0),
+                   burn_in_steps=training.get("burn_in_steps", 0), exploration=training.get("exploration", "imitative"),
                    adaptive_clipping=adaptive_clipping and bool(training.get("gradient_threshold")), **kw)
 
     # ---- what a restart needs besides the parameters (the reference pickles the whole main loop, serialization.py:145-262) --
@@ -399,7 +410,8 @@ class Trainer(object):
                     self._enqueue_optimizer(global_batch_size)
                     st.version += 1
                 return cm
-            cm = self.rec.cost_and_gradients(batch, region=self.dp_region, head=head, tail_key=self._noise_key())
+            cm = self.rec.cost_and_gradients(batch, region=self.dp_region, head=head, tail_key=self._noise_key(),
+                                             exploration=self.exploration)
             self.apply_gradients(global_batch_size)
             return cm
         gbs = global_batch_size if global_batch_size is not None else B_local
@@ -407,6 +419,6 @@ class Trainer(object):
         def tail():
             self._enqueue_guard()
             self._enqueue_optimizer(gbs)
-        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key, head=head)
+        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key, head=head, exploration=self.exploration)
         self.rec.store.version += 1
         return cm

@@ -352,6 +352,29 @@ int lvsr_act_bwd(void* stream, int kind, const float* x, int ldx, const float* d
 int lvsr_softmax_nll(void* stream, const float* logits, int ld, const long long* labels, const float* mask, int n, int V,
                      float* cost, float* dlogits, int ldd, float scale, float* neglogp, int ldn);
 
+/* ---- task-loss-estimation criteria (mse_gain / mse_reward) --------------------------------------------
+ * RewardOp.perform (lvsr/ops.py:236-294) over reward_matrix / gain_matrix (lvsr/error_rate.py:79-112), which the reference runs in
+ * host Python, as one work-group per utterance.  groundtruth (Lg,B), prediction (Lp,B) int64; rewards, gains (Lp,B,V) float32
+ * holding exact small integers; prediction_mask (Lp,B) or NULL.  Per utterance: y = the groundtruth column up to and including its
+ * first `eos` (labels must end in EOS; a column without one is used whole — the reference raises there, this kernel does not
+ * fault), n = index of the prediction's first `eos` + 1 (none: Lp).  For j < n, with col_j[i] the edit distance between y[:i] and
+ * prediction[:j]:  reward[j,c] = -min(min_i col_j[i] + 1, min{col_j[i] : i < |y|, y[i] = c}),  reward[j,eos] = -col_j[|y|-1],
+ * gain[0] = reward[0], gain[j] = reward[j] - reward[j-1, prediction[j-1]].  Rows j >= n: reward = -1, gain = -1000.
+ * prediction_mask[j] = (j < n) (lvsr/main.py:254-259).  Integer arithmetic throughout: bit-identical from run to run.
+ * Limits (LDS): Lg <= 1024 (RG_MAX_Y), V <= 2048 (RG_MAX_V); Lp is not limited. */
+int lvsr_reward_gain(void* stream, const long long* groundtruth, int Lg, const long long* prediction, int Lp, int B, int eos, int V,
+                     float* rewards, float* gains, float* prediction_mask);
+/* RewardRegressionEmitter.cost (lvsr/bricks/__init__.py:134-183) of readouts (L*B,V; row stride ld) with the mask of
+ * BaseSequenceGenerator.cost_matrix, and its gradient; takes the place of lvsr_softmax_nll.  labels = the prediction (L,B), m = mask
+ * (L,B) or NULL (ones).
+ *   mode 0 (mse_gain):   g = max(gain, min_reward); cost[l,b] = m sum_v (r - g)^2; dlogits = 2 m (r - g)
+ *   mode 1 (mse_reward): P[l,b] = sum_{k=1..l} r[k,b,labels[k,b]]; cost[l,b] = m sum_v (r + P - reward)^2; with e = 2 m (r + P - reward):
+ *                        dlogits[l,b,v] = e[l,b,v] + [l >= 1 and v = labels[l,b]] sum_{l' >= l} sum_v' e[l',b,v']   (L <= 4096)
+ * Every sum runs in a fixed order: eager launches and graph replays give the same bits.  Rows with m = 0 cost 0. */
+int lvsr_reward_mse(void* stream, int mode, const float* readouts, int ld, const float* gains, const float* rewards,
+                    const long long* labels, const float* mask, int L, int B, int V, float min_reward, float* cost, float* dlogits,
+                    int ldd);
+
 /* ---- optimiser step on the flat buffers -----------------------------------------------------------
  * StepClipping -> Momentum(scale) -> AdaDelta -> Restrict(VariableClipping(axis=0), WEIGHT params) ->
  * RemoveNotFinite -> [BurnIn] -> parameter -= step  (lvsr/main.py:480-519; libs/blocks/blocks/algorithms/__init__.py:
@@ -452,6 +475,10 @@ typedef struct lvsr_readout_step_args {
     /* R1 != NULL: the merged pre-activations (n,P) = S @ Wms + WA @ Wmw + bias1 have been computed by lvsr_readout_merge (row
      * stride ldr1); the per-row products above are skipped (S, WA, Wms, Wmw are not read) */
     const float* R1; int ldr1;
+    /* emitter: 0 = SoftmaxEmitter (above); 1 = RewardRegressionEmitter (lvsr/bricks/__init__.py:183-192) of the mse_gain / mse_reward
+     * criteria: neglogp = -readouts (`costs`), outputs = the first maximal class (`emit`: argmax, no uniforms needed; written when
+     * outputs != NULL) and costs[r] = +readouts[r, outputs[r]] (the 2-D branch of `cost`).  Not combined with lm_add */
+    int emitter;
 } lvsr_readout_step_args;
 int lvsr_readout_step(void* stream, const lvsr_readout_step_args* a);
 /* The merge of lvsr_readout_step for MANY rows (batched beam search: n = searches x beam): R1 (n,P) = S @ Wms + WA @ Wmw + bias1
