@@ -372,11 +372,11 @@ class SequenceGenerator(object):
     def cost_matrix(self, outputs, mask=None, attended=None, attended_mask=None, save_for_backward=True, groundtruth=None,
                     rewards=None):
         """outputs (L,B) int64 labels, mask (L,B) or None, attended (T',B,E), attended_mask (T',B) -> costs (L,B).
-        Also keeps `self.last` = dict(weights, energies, states, weighted_averages) (the auxiliary variables
+        Also keeps `self.last` = dict(weights, energies, states, weighted_averages, readouts) (the auxiliary variables
         `SpeechRecognizer.analyze` extracts, recognizer.py:452-494).
         mse criteria: `outputs` / `mask` are the prediction, `groundtruth` (Lg,B; default: `outputs`, the placeholder the reference's
         get_cost_graph swaps, recognizer.py:437-449) is what the rewards are measured against; `rewards`: the result of
-        `reward_matrices` when the caller has run it already.  `last` also holds readouts, gain_matrix and reward_matrix."""
+        `reward_matrices` when the caller has run it already.  `last` also holds gain_matrix and reward_matrix."""
         self._check_emitter()
         d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
         L, B = int(outputs.shape[0]), int(outputs.shape[1])
@@ -414,9 +414,9 @@ class SequenceGenerator(object):
                      float(lm.lm_weight), int(lm.norm[0]), int(lm.norm[1]), int(lm.norm[2]), 1.0, ptr(fused))
             lib.call("lvsr_select_cost", lib.stream_for(cost), ptr(fused), d.V, ptr(labels), ptr(ym), L * B, d.V, -1.0,
                      ptr(cost))
-        self.last = dict(weights=W[1:], energies=bufs["EN"], states=S[:L], weighted_averages=WA)
+        self.last = dict(weights=W[1:], energies=bufs["EN"], states=S[:L], weighted_averages=WA, readouts=logits.view(L, B, d.V))
         if self.mse:
-            self.last.update(readouts=logits.view(L, B, d.V), gain_matrix=rw["gains"], reward_matrix=rw["rewards"])
+            self.last.update(gain_matrix=rw["gains"], reward_matrix=rw["rewards"])
         if save_for_backward:
             self._saved = dict(L=L, B=B, Tp=Tp, A=A, Am=Am, PA=PA, labels=labels, ym=ym, bufs=bufs,
                                R1=R1, R2=R2, dlogits=dlogits, pk=pk, pm_acts=list(self._pm_acts))

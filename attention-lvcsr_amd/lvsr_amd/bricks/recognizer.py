@@ -184,9 +184,10 @@ class SpeechRecognizer(object):
                 self._t(labels, torch.int64, "labels"), self._t(labels_mask, torch.float32, "labels_mask"))
 
     def _forward(self, x, xm, y, ym, save_for_backward=True, groundtruth=None):
-        encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, save_for_backward), xm,
-                                                   save_for_backward=save_for_backward)
+        self.bottom_output = self.bottom.apply(x, save_for_backward)
+        encoded, encoded_mask = self.encoder.apply(self.bottom_output, xm, save_for_backward=save_for_backward)
         self.encoded, self.encoded_mask = encoded, encoded_mask
+        self.cost_mask = ym          # the mask the cost matrix is taken under (lvsr_amd/observables.py)
         return self.generator.cost_matrix(y, ym, attended=encoded, attended_mask=encoded_mask,
                                           save_for_backward=save_for_backward, groundtruth=groundtruth)
 
@@ -198,11 +199,13 @@ class SpeechRecognizer(object):
         prediction up to its first EOS, on the device), then the teacher-forced pass on the prediction.  No host synchronisation.
         -> cost matrix (L + 10, B)."""
         gen = self.generator
-        encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, True), xm, save_for_backward=True)
+        self.bottom_output = self.bottom.apply(x, True)
+        encoded, encoded_mask = self.encoder.apply(self.bottom_output, xm, save_for_backward=True)
         self.encoded, self.encoded_mask = encoded, encoded_mask
         prediction = gen.generate(n_steps=int(y.shape[0]) + self.LENGTH_EXPAND, attended=encoded, attended_mask=encoded_mask)["outputs"]
         rw = gen.reward_matrices(y, prediction, want_mask=True)
         self.prediction, self.prediction_mask = prediction, rw["mask"]
+        self.cost_mask = rw["mask"]
         return gen.cost_matrix(prediction, rw["mask"], attended=encoded, attended_mask=encoded_mask, rewards=rw)
 
     # ---- free-running generation (recognizer.py:393-406, 535-547) ------------------------------------------------------
@@ -268,7 +271,8 @@ class SpeechRecognizer(object):
         assert all(k.startswith("/recognizer/generator") == (o >= first) for k, (o, n) in offs.items()), "decoder parameters are not a tail"
         return first, self.store.flat.numel() - first
 
-    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None, head=None, exploration=None):
+    def cost_and_gradients(self, batch, tail=None, tail_key=None, region=True, between=None, head=None, exploration=None,
+                           after_forward=None):
         """One training forward+backward on a batch dict in the reference's layout.
         Returns the cost matrix (L,B) on the device; gradients of its sum are in self.store.grad.
         `tail` (optional callable, described by the hashable `tail_key`) enqueues more work behind the backward pass — the
@@ -278,6 +282,9 @@ class SpeechRecognizer(object):
         (forward + decoder backward | encoder backward [+ tail]).
         `head` (optional callable, described by `tail_key` as well) enqueues work in front of the forward pass inside the (first)
         graph region: the noisy weights of adaptive noise.
+        `after_forward` (optional callable, described by `tail_key` as well) enqueues work right behind the forward pass, inside the
+        graph region that holds the forward pass: it may use what the forward pass left on this object (`encoded`, `cost_mask`,
+        `generator.last`, ...), which a later replay of the region does not refresh — the training observables.
         `exploration`: None / "imitative" = the decoder is driven by the labels; "greedy" (mse criteria, `training.exploration` of the
         reference, lvsr/main.py:245-283) = by its own argmax prediction of L + 10 labels, generated inside the same graph region
         (`_forward_greedy`); the cost matrix is then (L + 10, B)."""
@@ -300,9 +307,11 @@ class SpeechRecognizer(object):
                     if head is not None:
                         head()
                     cm = self._forward(x, xm, y, ym)
+                    if after_forward is not None:
+                        after_forward()
                     return cm, self._backward_decoder()
 
-                key1 = ("train_step_fwd_dec",) + shape_key + ((tail_key,) if head is not None else ())
+                key1 = ("train_step_fwd_dec",) + shape_key + ((tail_key,) if head is not None or after_forward is not None else ())
                 cm, d_encoded = self.lib.region(self, key1, x, enabled=plain, volatile=volatile).run(first_half)
                 between()
 
@@ -319,6 +328,8 @@ class SpeechRecognizer(object):
                 if head is not None:
                     head()
                 cm = self._forward_greedy(x, xm, y) if greedy else self._forward(x, xm, y, ym)
+                if after_forward is not None:
+                    after_forward()
                 self.backward()
                 if tail is not None:
                     tail()

@@ -59,13 +59,55 @@ def validate(recognizer, data, part="valid"):
     return total / max(1, count)
 
 
+def validate_observables(recognizer, data, part="valid"):
+    """`validate` with the validation observables of lvsr/main.py:550-569: -> dict(cost, num_utterances, weights_entropy_per_label,
+    weights_penalty_per_recording) — the cost per utterance, the alignment entropy over the sum of the labels mask and the
+    monotonicity penalty over the number of utterances.  The sums stay on the device across the batches and are read once."""
+    from .observables import ValidationRecord
+    record, count = ValidationRecord(recognizer), 0
+    for batch in data.get_stream(part, shuffle=False):
+        cm = recognizer.cost(recordings=batch["recordings"], inputs_mask=batch["recordings_mask"], labels=batch["labels"],
+                             labels_mask=batch["labels_mask"], save_for_backward=False)
+        record.add(cm)
+        recognizer.encoder.check_persistent()         # (as in `validate`)
+        recognizer.generator.check_persistent()
+        count += int(batch["labels"].shape[1])
+    total, penalty, entropy, mask_sum = record.read()
+    return dict(cost=total / max(1, count), num_utterances=count, weights_entropy_per_label=entropy / max(1.0, mask_sum),
+                weights_penalty_per_recording=penalty / max(1, count))
+
+
+# the channels of a batch row that the `every`-th row averages (TrainingDataMonitoring(prefix="average"), lvsr/main.py:587-589)
+_AVERAGED = ("weights_penalty", "weights_entropy", "min_energy", "max_energy", "mean_attended", "mean_bottom_output", "mask_density",
+             "total_step_norm", "min_gain", "max_gain", "train_cost", "total_gradient_norm", "gradient_norm_threshold")
+
+
+def _average_row(window, iterations, epoch):
+    """The row behind every `every`-th batch: means of the channels over the window; the alignment channels under the
+    aggregation schemes of lvsr/main.py:555-569 (sum of penalties / sum of batch sizes, sum of entropies / sum of mask sums); the
+    per-parameter statistics averaged the same way."""
+    row = dict(iterations_done=iterations, epochs_done=epoch, average_over=len(window))
+    for k in _AVERAGED:
+        if k in window[0]:
+            row["average_" + k] = float(numpy.mean([w[k] for w in window]))
+    row["average_weights_penalty_per_recording"] = sum(w["weights_penalty"] for w in window) / sum(w["batch_size"] for w in window)
+    row["average_weights_entropy_per_label"] = sum(w["weights_entropy"] for w in window) / sum(w["mask_sum"] for w in window)
+    for k in window[0]:
+        if k.endswith("_stats"):
+            row[k] = numpy.mean([w[k] for w in window], axis=0)
+    return row
+
+
 def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=None, distributed=None, search_subset=10,
-          resume=False, stage=None):
+          resume=False, stage=None, observables=None):
     """One stage.  `config`: a (stage) configuration mapping with `net`, `training`, optional `regularization`,
     `monitoring`, `initialization`; `data`: lvsr_amd.data.Data.  Returns (recognizer, log).
     `resume=True`: `params` is a checkpoint of THIS stage written by an earlier call: besides the parameters, the optimiser
     accumulators, the adaptive-clipping statistics and the epoch / iteration / best-cost counters are restored from its
-    `_training_state` member, so the recipe continues where it stopped (the reference resumes from its pickled main loop)."""
+    `_training_state` member, so the recipe continues where it stopped (the reference resumes from its pickled main loop).
+    `observables` (or `monitoring: {observables: ...}`): True or dict(every=10, parameter_stats=True) — every batch row gains the
+    reference's primary channels, every `every`-th batch an `average_*` row with the per-parameter statistics follows, the epoch row
+    gains the two `valid_*` alignment channels (lvsr_amd/observables.py)."""
     from .config import Configuration
     log = [] if log is None else log
     reg = dict(config.get("regularization") or {})
@@ -90,8 +132,11 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
         rec.load_params(params)
     rank, world, barrier = _dist_state(distributed)
     # adaptive noise divides its model cost by the size of the training set (lvsr/main.py:434)
+    if observables is None:
+        observables = mon.get("observables")
     trainer = Trainer.from_config(rec, train_conf, config.get("regularization"), distributed=world > 1 or bool(distributed),
-                                  num_examples=data.datasets["train"].num_examples)
+                                  num_examples=data.datasets["train"].num_examples, **({"observables": observables} if observables else {}))
+    window = []                 # batch rows (with the observables' raw sums) since the last average row
     root, ext = os.path.splitext(save_path)
     best_ll, best_per, best_epoch = float("inf"), float("inf"), 0
     num_batches, num_epochs = train_conf.get("num_batches"), train_conf.get("num_epochs")
@@ -144,7 +189,17 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
                 row.update(trainer.noise_stats())
                 row["train_cost"] += row["model_cost"]
             costs.append(row["train_cost"])
+            average = None
+            if trainer.obs is not None:
+                # (float(cm.sum()) above has waited for the step: the record's host mirror is complete, reading it waits for nothing)
+                channels = trainer.observables()
+                window.append(dict(row, **channels))
+                row.update((k, v) for k, v in channels.items() if k != "mask_sum" and not k.endswith("_stats"))
+                if iterations % trainer.obs.every == 0:
+                    average, window = _average_row(window, iterations, epoch), []
             log.append(row)
+            if average is not None:
+                log.append(average)
             if not numpy.isfinite(row["total_gradient_norm"]):        # FinishAfter(...).add_condition(_gradient_norm_is_none)
                 row["training_finish_requested"] = "gradient norm is not finite"
                 done = True
@@ -157,7 +212,12 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
         if has_valid:
             # replicas are identical: every rank computes the same validation cost (keeps the stopping rules in step without
             # another collective); only rank 0 writes files
-            row["valid_cost"] = validate(rec, data, "valid")
+            if trainer.obs is not None:
+                valid = validate_observables(rec, data, "valid")
+                row.update(valid_cost=valid["cost"], valid_weights_entropy_per_label=valid["weights_entropy_per_label"],
+                           valid_weights_penalty_per_recording=valid["weights_penalty_per_recording"])
+            else:
+                row["valid_cost"] = validate(rec, data, "valid")
             if row["valid_cost"] < best_ll:
                 best_ll, best_epoch = row["valid_cost"], epoch
                 row["best_valid_cost_so_far"] = True

@@ -44,7 +44,7 @@ class Trainer(object):
     def __init__(self, recognizer, gradient_threshold=None, rules=("momentum",), scale=0.1, momentum=0.0,
                  decay_rate=0.95, epsilon=1e-8, max_norm=0.0, max_norm_exclude_lookup=False, nonfinite_scaler=0.0,
                  burn_in_steps=0, adaptive_clipping=None, process_group=None, distributed=None, dp_region=True,
-                 overlap_allreduce=False, adaptive_noise=None, num_examples=None, exploration="imitative"):
+                 overlap_allreduce=False, adaptive_noise=None, num_examples=None, exploration="imitative", observables=None):
         """Keywords = `training:` / `regularization:` keys of the reference's config (lvsr/main.py:480-519).
         `adaptive_clipping`: None, True or dict(decay_rate=0.998, burnin_period=500) — the AdaptiveClipping extension the
         reference's `train()` always installs on top of `gradient_threshold` (lvsr/main.py:616-619).
@@ -52,7 +52,10 @@ class Trainer(object):
         (lvsr/main.py:425-456, lvsr_amd/weight_noise.py); it needs `num_examples`, the size of the training set.  The step rules then
         run over theta = [means | log-variances] (max_norm on WEIGHT-role means only) and `store.flat` holds the means between steps.
         `exploration` (`training.exploration`, add_exploration, lvsr/main.py:245-283): 'imitative' = the labels drive the decoder;
-        'greedy' (mse criteria) = its own argmax prediction does (SpeechRecognizer.cost_and_gradients); 'mixed' is not built."""
+        'greedy' (mse criteria) = its own argmax prediction does (SpeechRecognizer.cost_and_gradients); 'mixed' is not built.
+        `observables`: None, True or dict(every=10, parameter_stats=True) — the reference's monitored channels (lvsr/main.py:317-396,
+        526-569) computed on the device around the optimiser step, inside the step's graph region (lvsr_amd/observables.py); read
+        them with `observables()`.  Off: not one launch more, and the graph-region keys of a trainer without them."""
         if exploration == "mixed":
             raise NotImplementedError("exploration 'mixed' (a Bernoulli draw per utterance between prediction and labels) is not built")
         if exploration not in ("imitative", "greedy"):
@@ -64,6 +67,11 @@ class Trainer(object):
         self.exploration = exploration
         from .weight_noise import settings as noise_settings
         noise_conf = noise_settings(adaptive_noise)
+        from .observables import settings as observables_settings
+        obs_conf = observables_settings(observables)
+        if obs_conf is not None and obs_conf["parameter_stats"] and noise_conf is not None:
+            raise NotImplementedError("observables.parameter_stats with adaptive_noise is not built (the rules run over [means | "
+                                      "log-variances]; pass observables=dict(parameter_stats=False))")
         if noise_conf is not None and num_examples is None:
             raise ValueError("adaptive_noise needs num_examples (the number of examples of the training set, lvsr/main.py:434)")
         self.rec = recognizer
@@ -141,6 +149,10 @@ class Trainer(object):
         self._reserve_before = None   # while a recovery's reserve is in force: the value of the knob to give back
         self._last_abort_step = None
         self.steps_done = 0
+        self.obs = None
+        if obs_conf is not None:
+            from .observables import Observables
+            self.obs = Observables(self, **obs_conf)
 
     @classmethod
     def from_config(cls, recognizer, training, regularization=None, adaptive_clipping=True, num_examples=None, **kw):
@@ -201,6 +213,12 @@ class Trainer(object):
             raise ValueError("this trainer runs without adaptive noise")
         return self.noise.observables()
 
+    def observables(self):
+        """dict of the last step's observables, named as in the reference (lvsr_amd/observables.py; synchronises)."""
+        if self.obs is None:
+            raise ValueError("this trainer runs without observables")
+        return self.obs.read()
+
     def _enqueue_guard(self):
         """Behind the backward pass: store.guard[0] = number of persistent cluster launches of this step that gave up waiting (the
         abort words in front of their workspaces).  The optimiser skips the step on the device when it is non-zero; under data
@@ -221,7 +239,11 @@ class Trainer(object):
                      ms_dx=self.ms_dx, step=self.step_buf, segments=self.segments, segflag=self.segflag,
                      scratch=self.scratch, n=param.numel(), nseg=int(self.segments.shape[0]), max_cols=self.max_cols,
                      grad_scale=scale, clip_state=self.clip_state, guard=st.guard, **self.conf)
+        if self.obs is not None:          # the parameter as the gradient saw it: in front of the update
+            self.obs.enqueue_before(param, grad, scale)
         lib.call("lvsr_opt_step", lib.stream_for(st.flat), ctypes.byref(a))
+        if self.obs is not None:
+            self.obs.enqueue_after(self.step_buf)
         if self.noise is not None:
             self.noise.publish()          # store.flat <- the means (a skipped step included)
         if self._skip_host is not None:
@@ -359,9 +381,10 @@ class Trainer(object):
         if ref.is_cuda and self._comm is not None:
             torch.cuda.current_stream(ref.device).wait_stream(self._comm)
 
-    def _noise_key(self):
-        """What the head / rewrite of adaptive noise add to a step's graph-region key (nothing without it)."""
-        return () if self.noise is None else (self._token,) + self.noise.key()
+    def _extras_key(self):
+        """What the head / rewrite of adaptive noise and the observables add to a step's graph-region key (nothing without them)."""
+        key = () if self.noise is None else (self._token,) + self.noise.key()
+        return key if self.obs is None else key + (self._token,) + self.obs.key()
 
     def apply_gradients(self, global_batch_size):
         rec, st = self.rec, self.rec.store
@@ -380,7 +403,12 @@ class Trainer(object):
         under data parallelism it is obtained by reducing the shard sizes."""
         B_local = int(batch["labels"].shape[1])
         self._before_step()
+        if self.obs is not None:
+            self.obs.begin_step(batch)
         head = None
+        # the alignment and tensor channels are enqueued behind the forward pass inside ITS graph region (data parallelism: the
+        # optimiser runs eagerly behind the all-reduce, and a replayed region leaves no fresh views of the forward pass behind)
+        watch = self.obs.enqueue_inputs if self.obs is not None else None
         if self.noise is not None:
             # the head of the step writes the noisy weights into store.flat: cached packs of the weights must be rebuilt
             self.rec.store.version += 1
@@ -402,7 +430,7 @@ class Trainer(object):
                     with rec._on_stream():
                         self._all_reduce(st.grad[off: off + cnt], wait=False)
                 cm = rec.cost_and_gradients(batch, region=self.dp_region, between=reduce_decoder_bucket, head=head,
-                                            tail_key=self._noise_key())
+                                            tail_key=self._extras_key(), after_forward=watch)
                 with rec._on_stream():
                     self._enqueue_guard()
                     self._all_reduce(st.grad_bucket[: 4 + off], wait=False)          # [guard | encoder gradients]
@@ -410,15 +438,16 @@ class Trainer(object):
                     self._enqueue_optimizer(global_batch_size)
                     st.version += 1
                 return cm
-            cm = self.rec.cost_and_gradients(batch, region=self.dp_region, head=head, tail_key=self._noise_key(),
-                                             exploration=self.exploration)
+            cm = self.rec.cost_and_gradients(batch, region=self.dp_region, head=head, tail_key=self._extras_key(),
+                                             exploration=self.exploration, after_forward=watch)
             self.apply_gradients(global_batch_size)
             return cm
         gbs = global_batch_size if global_batch_size is not None else B_local
-        tail_key = ("opt", self._token, float(gbs), tuple(sorted(self.conf.items()))) + self._noise_key()
+        tail_key = ("opt", self._token, float(gbs), tuple(sorted(self.conf.items()))) + self._extras_key()
         def tail():
             self._enqueue_guard()
             self._enqueue_optimizer(gbs)
-        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key, head=head, exploration=self.exploration)
+        cm = self.rec.cost_and_gradients(batch, tail=tail, tail_key=tail_key, head=head, exploration=self.exploration,
+                                         after_forward=watch)
         self.rec.store.version += 1
         return cm

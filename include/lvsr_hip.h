@@ -449,6 +449,59 @@ int lvsr_wnoise_grad(void* stream, const lvsr_wnoise_args* a);
  * z[4 b + j] = the normal of element 4 q + j, raw[4 b + j] = the Philox word x_j (raw may be NULL). */
 int lvsr_philox_normal(void* stream, long long seed, long long counter, long long first, long long nblocks, float* z, unsigned* raw);
 
+/* ---- training / validation observables (lvsr/main.py:317-396, 526-569; lvsr/expressions.py:14-25) -------------------------
+ * What the reference's train() monitors besides the cost, as reductions on the device behind the backward pass, so that a training
+ * step stays one graph and nothing but a few dozen numbers is copied to the host (csrc/observables.hip).  No floating-point atomics:
+ * every sum has an order fixed by the sizes alone — eager launches, captured launches, graph replays and two runs give the same bits.
+ * Quantities of one row are float32 where the reference's are; sums across rows, work-groups or tensors are float64, rounded once.
+ *
+ * lvsr_alignment_stats: the alignment channels.  Row (l,b) of `weights` (L,B,T') starts at weights + (l B + b) ldw (ldw >= T';
+ * the live buffer is the slice [1:] of an (L+1,B,T') tensor), mask (L,B) or NULL (ones).  With C[l,b,t] = w[l,b,0] + ... + w[l,b,t]
+ * (each row's cumulative sum taken on its own, then subtracted, as monotonicity_penalty does):
+ *   out[0] weights_penalty = sum_{l>=1,b} mask[l,b] sum_t max(C[l,b,t] - C[l-1,b,t], 0)        (L = 1: 0)
+ *   out[1] weights_entropy = sum_{l,b} mask[l,b] sum_t w logf(w + 1e-7f)      (the reference's sign; an exact zero contributes 0)
+ *   out[2] mask_sum        = sum mask
+ * One wave per row, lanes strided over T': the cumulative sum is a 64-lane scan with a carry from chunk to chunk, the row's terms
+ * are folded by the xor tree, times the mask in float32; partials (2 L B doubles, scratch) are then added by one work-group.
+ * accumulate != 0: out[k] += (validation: one record over all batches), else out[k] =. */
+int lvsr_alignment_stats(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask,
+                         double* partials, double* out, int accumulate);
+/* out[0] = min, out[1] = max (both exact; float32 values held in doubles), out[2] = sum |x| over the n contiguous floats of x;
+ * use_floor != 0: over max(x, floor) instead (the gain matrix as RewardRegressionEmitter.cost sees it, lvsr/bricks/__init__.py:154).
+ * Two stages: ceil(n / 8192) work-groups (at most 1024: the grid depends on n only) with float64 sums per thread and a fixed
+ * tree per work-group, then one work-group over `partials` (3 * 1024 doubles, scratch).  A NaN element is ignored by min / max and
+ * poisons the sum; which of +0 and -0 is the minimum (maximum) of a buffer that holds both and nothing smaller (larger) is not defined. */
+int lvsr_tensor_stats(void* stream, const float* x, long long n, int use_floor, float floor, double* partials, double* out);
+/* Per-parameter norms of a training step over the optimiser's own tables (lvsr_opt_args: segments, param, grad, step), and the total
+ * step norm.  `items` (nitems,3) int64 = work items (segment, start inside the segment, count <= 8192) built once by the host, those of
+ * a segment consecutive and in order of `start`, items [seg_first[s], seg_first[s+1]) belonging to segment s (seg_first: nseg + 1
+ * ints); one work-group per item writes three float64 partials, one work-group per segment adds its items' partials in a fixed order.
+ *   out[s] = [ ||p|| , ||g grad_scale|| , ||step|| , ||step|| / ||g grad_scale|| ] / sqrt(elements of s)  (the ratio: not divided)
+ * float32 (nseg,4), the quotient taken on the rounded float32 norms (a zero gradient gives inf or nan, as the reference's division);
+ * segsums (nseg,3) float64 = the sums of squares; *total = sqrt(sum_s step sums) = total_step_norm.
+ * TWO launches around lvsr_opt_step, because the reference's monitored parameter is the one the gradient was taken at:
+ *   phase 1, in front of the optimiser: the partials of p (before the update) and of g grad_scale;
+ *   phase 2, behind it: the partials of `step`, then the sums, `out` and `total`;  phase 3 = both at once (static buffers: tests).
+ * `step` after lvsr_opt_step is the step behind clipping, the rules and max-norm, but in front of RemoveNotFinite and BurnIn, which
+ * its last kernel applies on the fly; the reference's algorithm.steps are behind them, so phase 2 accounts for them from the
+ * optimiser's own words (all optional, NULL = off): scratch[3] != 0 (guarded step skipped) or clip_state with scratch[2] != 0
+ * (burn-in) -> the step is zero; remove_not_finite and segflag[s] -> the step of segment s is (1 - nonfinite_scaler) p. */
+typedef struct lvsr_segnorm_args {
+    const float* param; const float* grad; const float* step;      /* flat buffers of lvsr_opt_args */
+    const long long* segments;            /* (nseg,4): offset, rows, cols, flags (flags are not read) */
+    const long long* items;               /* (nitems,3) */
+    const int* seg_first;                 /* (nseg+1) */
+    int nseg, nitems;
+    float grad_scale, nonfinite_scaler;
+    int remove_not_finite, pad0;
+    const int* segflag; const float* scratch; const double* clip_state;      /* of the lvsr_opt_step in between, or NULL */
+    double* partials;                     /* (nitems,3) scratch, carried from phase 1 to phase 2 */
+    double* segsums;                      /* (nseg,3) out */
+    float* out;                           /* (nseg,4) out */
+    double* total;                        /* (1) out */
+} lvsr_segnorm_args;
+int lvsr_segment_norms(void* stream, const lvsr_segnorm_args* a, int phase);
+
 /* Generation-time readout + emitter of n rows in one launch (one work-group per row):
  * Readout.readout (libs/blocks/blocks/bricks/sequence_generators.py:614-619) with the post-merge stack of
  * lvsr/bricks/recognizer.py:298-320, then SoftmaxEmitter.costs (:788-791) or, with lm_add, ShallowFusionReadout + LMEmitter
