@@ -11,6 +11,8 @@
 #include "common.h"
 #include "lvsr_hip.h"
 #include "graph_cache.h"
+#include <algorithm>
+#include <vector>
 
 #define BM 64
 #define BN 64
@@ -202,8 +204,9 @@ __device__ __forceinline__ int gemm_xcd_order(int L, int total) {
 // one TM x TN output tile (bx, by) of k-chunk / batch member bz.  TM = TN = 128: four waves of 64 x 64 (2 x 2 MFMA 32x32 blocks);
 // TM = TN = 64: four waves of 32 x 32 (one block each) — for outputs of a few hundred 64-tiles that leave most of the chip idle as
 // 128-tiles (the decoder's L*B- and T'*B-row products: 13 x 4 tiles of 128 against 25 x 8 of 64 over 512 resident work-groups)
+// `fast`: the same condition per call, for a launch whose work-groups serve operands of mixed alignment (the grouped launch)
 template <int TM, int TN, bool TA, bool TB, bool FAST>
-__device__ __forceinline__ void sgemm_tile(GemmArgs g, int bx, int by, int bz) {
+__device__ __forceinline__ void sgemm_tile(GemmArgs g, int bx, int by, int bz, bool fast = true) {
     constexpr int MI = TM / 64, NI = TN / 64;                 // MFMA blocks per wave
     __shared__ __attribute__((aligned(16))) float As[2][TM][GLD];
     __shared__ __attribute__((aligned(16))) float Bs[2][TN][GLD];
@@ -226,7 +229,7 @@ __device__ __forceinline__ void sgemm_tile(GemmArgs g, int bx, int by, int bz) {
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     float4 ra[TM / 32], rb[TN / 32];
     // A: not transposed -> (m,k) at A[m*lda+k] (contiguous k); transposed -> A[k*lda+m] (contiguous m)
-    const bool inside = FAST && m0 + TM <= g.M && n0 + TN <= g.N;
+    const bool inside = FAST && fast && m0 + TM <= g.M && n0 + TN <= g.N;
     if (inside && kbeg + GK <= kend) {
         gemm2_tile_load<!TA, TM, false>(g.A, g.lda, m0, g.M, kbeg, kend, true, ra);
         gemm2_tile_load<TB, TN, false>(g.B, g.ldb, n0, g.N, kbeg, kend, true, rb);
@@ -466,7 +469,9 @@ __device__ __forceinline__ void sgemm_tile_kmajor(GemmArgs g, int bx, int by, in
             }
 }
 template <bool TA, bool TB, bool FAST>
-__device__ __forceinline__ void sgemm128_tile(GemmArgs g, int bx, int by, int bz) { sgemm_tile<128, 128, TA, TB, FAST>(g, bx, by, bz); }
+__device__ __forceinline__ void sgemm128_tile(GemmArgs g, int bx, int by, int bz, bool fast = true) {
+    sgemm_tile<128, 128, TA, TB, FAST>(g, bx, by, bz, fast);
+}
 
 template <bool TA, bool TB, bool FAST>
 __global__ __launch_bounds__(256) void lvsr_sgemm64_kernel(GemmArgs g) {
@@ -489,16 +494,22 @@ __global__ __launch_bounds__(256) void lvsr_sgemm128_kernel(GemmArgs g) {
 // on a handful of work-groups at 26 us per launch.  Together their (problem, tile, k-chunk) units fill the chip with ~1 000-deep
 // chunks in ONE launch, and one more launch folds all partials in a fixed order (deterministic).
 #define GROUP_MAX 40
+#define FOLD_ELEMS 1024                     // outputs per fold work-group
 struct GroupDesc {
     const float* A; const float* B; float* C;
     int M, N, K, lda, ldb, ldc;
     float beta;
-    int ksplit, kchunk, gx, gy, unit0;      // tiles gx x gy, ksplit chunks; unit0 = first unit of this problem in the launch
-    long long part_off;                     // offset (floats) of this problem's partials in the workspace
+    int ksplit, kchunk, gx, gy;             // tiles gx x gy, ksplit chunks
+    int unit0;                              // first unit of this problem in the launch
+    int fast;                               // operands 16-B aligned with ld % 4 == 0: unguarded loads for the inner tiles
+    int fold0;                              // first fold work-group of this problem (none when ksplit == 1)
+    long long part_off;                     // offset (floats, a multiple of 4) of this problem's partials in the workspace
 };
 struct GroupPack { GroupDesc d[GROUP_MAX]; int n, total; float* part; };
 
-template <bool FAST>
+// The units of the launch in the order of the problems (deepest units first), per problem (k-chunk, m-tile, n-tile), n fastest; every
+// XCD takes one contiguous run of that sequence (gemm_xcd_order), so the tiles of a k-chunk, which share operand panels, meet in one L2.
+// A work-group picks the aligned or the guarded loads by its problem's `fast`: one launch for members of either kind.
 __global__ __launch_bounds__(256) void lvsr_sgemm128_grouped_tn_kernel(GroupPack pk) {
     const int t = gemm_xcd_order(blockIdx.x, pk.total);
     int p = 0;
@@ -511,21 +522,69 @@ __global__ __launch_bounds__(256) void lvsr_sgemm128_grouped_tn_kernel(GroupPack
     g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.transA = 1; g.transB = 0;
     g.alpha = 1.f; g.beta = d.beta; g.ksplit = d.ksplit; g.kchunk = d.kchunk; g.part = pk.part + d.part_off;
     g.batch = 1; g.sA = g.sB = g.sC = 0;
-    sgemm128_tile<true, false, FAST>(g, local % d.gx, (local / d.gx) % d.gy, local / (d.gx * d.gy));
+    sgemm128_tile<true, false, true>(g, local % d.gx, (local / d.gx) % d.gy, local / (d.gx * d.gy), d.fast != 0);
 }
 
-// blockIdx.y = problem; its blocks stride over the output elements and fold the k-chunks in order
+// The fold: FOLD_ELEMS outputs of one problem per work-group, four per thread (one float4 where N, ldc and the addresses allow,
+// else four scalars a row of threads apart), the loads of four k-chunks in flight at a time.  Per output: s = sum of the partials
+// in ascending chunk order, then + beta * C.
 __global__ __launch_bounds__(256) void lvsr_sgemm_grouped_reduce(GroupPack pk) {
-    const GroupDesc& d = pk.d[blockIdx.y];
-    if (d.ksplit <= 1) return;
+    int p = 0;
+    for (int x = 1; x < pk.n; ++x)
+        if ((int)blockIdx.x >= pk.d[x].fold0) p = x;
+    const GroupDesc& d = pk.d[p];
     const size_t total = (size_t)d.M * d.N;
     const float* part = pk.part + d.part_off;
-    for (size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (size_t)gridDim.x * 256) {
-        const int m = (int)(idx / d.N), n = (int)(idx % d.N);
-        float s = 0.f;
-        for (int z = 0; z < d.ksplit; ++z) s += part[(size_t)z * total + idx];
-        if (d.beta != 0.f) s += d.beta * d.C[(size_t)m * d.ldc + n];
-        d.C[(size_t)m * d.ldc + n] = s;
+    const size_t base = (size_t)((int)blockIdx.x - d.fold0) * FOLD_ELEMS;
+    const bool vec = (d.N & 3) == 0 && (d.ldc & 3) == 0 && (((size_t)d.C) & 15) == 0 && (((size_t)part) & 15) == 0;
+    size_t idx[4];
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) idx[e] = vec ? base + 4 * threadIdx.x + e : base + threadIdx.x + 256 * e;
+    int z = 0;
+    if (vec) {
+        if (idx[0] >= total) return;
+        const float* q = part + idx[0];
+        for (; z + 4 <= d.ksplit; z += 4) {
+            float4 v[4];
+#pragma unroll
+            for (int c = 0; c < 4; ++c) v[c] = *(const float4*)(q + (size_t)(z + c) * total);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) { s[0] += v[c].x; s[1] += v[c].y; s[2] += v[c].z; s[3] += v[c].w; }
+        }
+        for (; z < d.ksplit; ++z) {
+            const float4 v = *(const float4*)(q + (size_t)z * total);
+            s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
+        }
+        float* c = d.C + (idx[0] / d.N) * d.ldc + idx[0] % d.N;
+        if (d.beta != 0.f) {
+            const float4 o = *(const float4*)c;
+            s[0] += d.beta * o.x; s[1] += d.beta * o.y; s[2] += d.beta * o.z; s[3] += d.beta * o.w;
+        }
+        *(float4*)c = make_float4(s[0], s[1], s[2], s[3]);
+        return;
+    }
+    for (; z + 4 <= d.ksplit; z += 4) {
+        float v[4][4];
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[c][e] = idx[e] < total ? part[(size_t)(z + c) * total + idx[e]] : 0.f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] += v[c][e];
+    }
+    for (; z < d.ksplit; ++z)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s[e] += idx[e] < total ? part[(size_t)z * total + idx[e]] : 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        if (idx[e] >= total) continue;
+        float* c = d.C + (idx[e] / d.N) * d.ldc + idx[e] % d.N;
+        float r = s[e];
+        if (d.beta != 0.f) r += d.beta * *c;
+        *c = r;
     }
 }
 
@@ -783,63 +842,93 @@ int lvsr_sgemm_batched(void* stream, int transA, int transB, int M, int N, int K
                         strideA, strideB, strideC);
 }
 
+// ---- the cut of a grouped call: k-chunks per member, and the order of the members inside a launch ----------------------------------
+// k-chunk depth: ~1024 where the partials of ALL members fit the workspace, else the smallest common depth that fits (starving
+// the members that come last of their splits instead left them as long serial tails: WSJ-deep 108 -> 113 ms); without a workspace
+// one chunk per tile.  The chunk boundaries fix the order of every sum, so the cut is a function of K and the workspace size alone:
+// per-member depths that balance the launch change the last bits of the gradients, and a training run does not forgive that
+// (DESIGN.md section 3.3).  What the launch is free to choose is where its units run — group_order.
+static bool group_aligned(const lvsr_gemm_desc& s) {
+    return (s.lda & 3) == 0 && (s.ldb & 3) == 0 && (((size_t)s.A) & 15) == 0 && (((size_t)s.B) & 15) == 0;
+}
+static void group_cut(const lvsr_gemm_desc* s, int n, long long ws_bytes, int* ksplit, int* kchunk) {
+    int target = 1024;
+    if (ws_bytes > 0) {
+        for (;; target += 512) {
+            long long need = 0;
+            bool splits = false;
+            for (int i = 0; i < n; ++i) {       // (a member's partials are rounded up to 16 bytes, so that the next member's stay aligned)
+                const int want = (s[i].K + target - 1) / target;
+                if (want > 1) { need += ((long long)want * s[i].M * s[i].N + 3) / 4 * 4; splits = true; }
+            }
+            if (!splits || need * 4 <= ws_bytes) break;
+        }
+    }
+    for (int i = 0; i < n; ++i) {
+        const int want = ws_bytes > 0 ? (s[i].K + target - 1) / target : 1;
+        int chunk = (s[i].K + want - 1) / want;
+        chunk = ((chunk + GK - 1) / GK) * GK;
+        kchunk[i] = chunk;
+        ksplit[i] = (s[i].K + chunk - 1) / chunk;
+    }
+}
+// members of one launch by falling unit cost (k-tiles of a chunk, a k-tile on the guarded scalar loads counting 2): the deepest units
+// are dispatched first, whatever order the caller collected them in.  (At the WSJ-base step the order measured no difference, 430.4
+// against 430.5 us: its one guarded member already comes first.  What the merged launch gains there is the guarded launch itself.)
+static void group_order(const lvsr_gemm_desc* s, const int* kchunk, int n, int* order) {
+    for (int i = 0; i < n; ++i) order[i] = i;
+    auto cost = [&](int i) { return (kchunk[i] < s[i].K ? kchunk[i] : s[i].K) * (group_aligned(s[i]) ? 1 : 2); };
+    std::stable_sort(order, order + n, [&](int a, int b) { return cost(a) > cost(b); });
+}
+
+int lvsr_sgemm_tn_grouped_plan(const lvsr_gemm_desc* descs, int n, long long ws_bytes, int* ksplit, int* kchunk) {
+    LVSR_REQUIRE(n >= 0 && (n == 0 || (descs && ksplit && kchunk)), "lvsr_sgemm_tn_grouped_plan: bad arguments");
+    for (int i = 0; i < n; ++i)
+        LVSR_REQUIRE(descs[i].M > 0 && descs[i].N > 0 && descs[i].K > 0, "lvsr_sgemm_tn_grouped_plan: bad descriptor %d", i);
+    group_cut(descs, n, ws_bytes, ksplit, kchunk);
+    return LVSR_OK;
+}
+
 int lvsr_sgemm_tn_grouped(void* stream, const lvsr_gemm_desc* descs, int n, float* ws, long long ws_bytes) {
     LVSR_REQUIRE(n >= 0 && (n == 0 || descs), "lvsr_sgemm_tn_grouped: bad arguments");
     hipStream_t st = (hipStream_t)stream;
     for (int i = 0; i < n; ++i)
         LVSR_REQUIRE(descs[i].A && descs[i].B && descs[i].C && descs[i].M > 0 && descs[i].N > 0 && descs[i].K > 0,
                      "lvsr_sgemm_tn_grouped: bad descriptor %d", i);
-    auto aligned = [](const lvsr_gemm_desc& s) {
-        return (s.lda & 3) == 0 && (s.ldb & 3) == 0 && (((size_t)s.A) & 15) == 0 && (((size_t)s.B) & 15) == 0;
-    };
-    // k-chunk depth: ~1024 where the partials of ALL members fit the workspace, else the smallest common depth that fits (starving
-    // the members that come last of their splits instead left them as long serial tails: WSJ-deep 108 -> 113 ms)
-    int target = 1024;
-    if (ws) {
-        for (;; target += 512) {
-            long long need = 0;
-            bool splits = false;
-            for (int i = 0; i < n; ++i) {
-                const int want = (descs[i].K + target - 1) / target;
-                if (want > 1) { need += (long long)want * descs[i].M * descs[i].N; splits = true; }
-            }
-            if (!splits || need * 4 <= ws_bytes) break;
-        }
-    }
-    // two passes: the problems whose operands allow unguarded 16-byte loads share the fast kernel, the others the guarded one
-    // (one misaligned member — the V-wide output-layer gradient — would otherwise put the whole group on the guarded loads)
+    if (!ws || ws_bytes < 0) ws_bytes = 0;
+    std::vector<int> ksplit(n), kchunk(n);
+    group_cut(descs, n, ws_bytes, ksplit.data(), kchunk.data());
+    // GROUP_MAX members per launch, in the order given; aligned and misaligned members share it (a per-member flag)
     long long off = 0;
-    for (int pass = 0; pass < 2; ++pass) {
+    for (int i0 = 0; i0 < n; i0 += GROUP_MAX) {
+        const int cnt = n - i0 < GROUP_MAX ? n - i0 : GROUP_MAX;
+        int order[GROUP_MAX];
+        group_order(descs + i0, kchunk.data() + i0, cnt, order);
         GroupPack pk;
-        pk.n = 0; pk.part = ws;
-        int units = 0;
-        bool any_split = false;
-        auto launch = [&]() {
-            if (pk.n == 0) return;
-            pk.total = units;
-            if (pass == 0) hipLaunchKernelGGL(lvsr_sgemm128_grouped_tn_kernel<true>, dim3(units), dim3(256), 0, st, pk);
-            else hipLaunchKernelGGL(lvsr_sgemm128_grouped_tn_kernel<false>, dim3(units), dim3(256), 0, st, pk);
-            if (any_split) hipLaunchKernelGGL(lvsr_sgemm_grouped_reduce, dim3(32, pk.n), dim3(256), 0, st, pk);
-            pk.n = 0; units = 0; any_split = false;
-        };
-        for (int i = 0; i < n; ++i) {
+        pk.n = cnt; pk.part = ws;
+        int units = 0, nfold = 0;
+        for (int o = 0; o < cnt; ++o) {
+            const int i = i0 + order[o];
             const lvsr_gemm_desc& s = descs[i];
-            if (aligned(s) != (pass == 0)) continue;
-            if (pk.n == GROUP_MAX) launch();
-            GroupDesc& d = pk.d[pk.n++];
+            GroupDesc& d = pk.d[o];
             d.A = s.A; d.B = s.B; d.C = s.C; d.M = s.M; d.N = s.N; d.K = s.K; d.lda = s.lda; d.ldb = s.ldb; d.ldc = s.ldc; d.beta = s.beta;
             d.gx = (s.N + GN - 1) / GN; d.gy = (s.M + GM - 1) / GM;
-            int want = ws ? (s.K + target - 1) / target : 1;
-            int chunk = (s.K + want - 1) / want;
-            chunk = ((chunk + GK - 1) / GK) * GK;
-            d.kchunk = chunk;
-            d.ksplit = (s.K + chunk - 1) / chunk;
-            d.part_off = off;
-            if (d.ksplit > 1) { off += (long long)d.ksplit * s.M * s.N; any_split = true; }
+            d.ksplit = ksplit[i]; d.kchunk = kchunk[i];
+            d.fast = group_aligned(s) ? 1 : 0;
             d.unit0 = units;
             units += d.gx * d.gy * d.ksplit;
+            d.fold0 = nfold;
+            d.part_off = off;
+            if (d.ksplit > 1) {
+                const long long mn = (long long)s.M * s.N;
+                off += (d.ksplit * mn + 3) / 4 * 4;
+                nfold += (int)((mn + FOLD_ELEMS - 1) / FOLD_ELEMS);
+            }
         }
-        launch();
+        LVSR_REQUIRE(off * 4 <= ws_bytes, "lvsr_sgemm_tn_grouped: partials exceed the workspace");
+        pk.total = units;
+        hipLaunchKernelGGL(lvsr_sgemm128_grouped_tn_kernel, dim3(units), dim3(256), 0, st, pk);
+        if (nfold) hipLaunchKernelGGL(lvsr_sgemm_grouped_reduce, dim3(nfold), dim3(256), 0, st, pk);
     }
     return lvsr_check_launch("lvsr_sgemm_tn_grouped");
 }

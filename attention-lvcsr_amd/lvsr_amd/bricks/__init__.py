@@ -425,8 +425,9 @@ class Encoder(object):
                 # fork gradients of both directions: one (I, 6H) product and one column sum, scattered into the four matrices
                 gW = ws.get("enc%d.gWcat" % i, (I, 6 * H))
                 gb = ws.get("enc%d.gbcat" % i, (6 * H,))
-                # (not a member of the grouped launch: with 48 output tiles it fills the chip alone, and the group's one-size k-chunks
-                # would cost it 13 instead of 5 partial copies of its 3 MB output — measured slower)
+                # (not a member of the grouped launch: with 48 output tiles it fills the chip alone, and the group's common ~1024-deep
+                # k-chunks would cost it 13 instead of 5 partial copies of its 3 MB output; as a member with a depth of its own it
+                # measured 886 us for the one launch against 381 + 528 us apart — nothing)
                 lib.sgemm(x2, dxg2, gW, transA=True, ws=side_ws)
                 colsum(dxg2, gb)
                 for di, direction in enumerate(("forward", "backward")):

@@ -77,6 +77,9 @@ typedef struct lvsr_gemm_desc {
     float beta;
 } lvsr_gemm_desc;
 int lvsr_sgemm_tn_grouped(void* stream, const lvsr_gemm_desc* descs, int n, float* ws, long long ws_bytes);
+/* How lvsr_sgemm_tn_grouped cuts the same member list given `ws_bytes` of workspace (<= 0: none): ksplit[i] k-chunks of kchunk[i]
+ * rows for member i (the last one shorter).  A function of the members' M, N, K and ws_bytes only. */
+int lvsr_sgemm_tn_grouped_plan(const lvsr_gemm_desc* descs, int n, long long ws_bytes, int* ksplit, int* kchunk);
 /* n independent strided 2-D copies (dst[r*ldd + c] = src[r*lds + c]) in ONE launch per 32 descriptors: the concatenated
  * fork weights of the encoder layers ((I,6H) = [Wi_f | Wg_f | Wi_b | Wg_b], refreshed per step) and the scatter of their
  * gradient back into the four parameters were 8 copy kernels of ~5 us per layer and pass. */
