@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #define LVSR_OK 0
 #define LVSR_ERR_ARG (-1)
@@ -29,6 +30,15 @@ int lvsr_max_cluster_wgs();
             return LVSR_ERR_ARG;                \
         }                                       \
     } while (0)
+
+// Host-side template dispatch: f(std::integral_constant<int, V>()) for the V among Vs... that equals v (the last one when none does),
+// so that a launch site names its kernel template once — a generic lambda over the compile-time value — instead of once per case.
+template <int V, int... Vs, class F>
+static inline void lvsr_dispatch(int v, F&& f) {
+    if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>());
+    else if (v == V) f(std::integral_constant<int, V>());
+    else lvsr_dispatch<Vs...>(v, f);
+}
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 // The same functions on the hardware transcendental units (v_exp_f32, v_rcp_f32: 1 ulp each; ~6 instructions instead of ~25 /

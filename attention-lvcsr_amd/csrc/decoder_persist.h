@@ -2,6 +2,7 @@
 #pragma once
 #include "decoder.h"
 #include "persist.h"
+#include <string.h>
 
 #define PD_THREADS 512       // two waves per SIMD: with one, every LDS / transcendental latency of the energy phase is exposed
 #define PD_CH 16             // attended positions per energy round (8 per half of the work-group)
@@ -36,21 +37,31 @@ typedef PdShape<32, 16, 2> PdShape8;
 typedef PdShape<16, 8, 2> PdShape16;
 typedef PdShape<16, 16, 1> PdShape32;
 
+// ---- the host-side launch plan, shared by the forward and the backward launches ---------------------------------------------------
+// Sizes are computed ONCE: what a *_ws_bytes query returns and what the launch clears come from the same layout function (pd_planes_bytes /
+// pb_planes_bytes beside each file's plane constants), accept / refuse decisions from the same geometry function the launch runs.
+
 // Which shape serves (B, D, M): LVSR_KNOB_DEC_CLUSTER 0 = clusters of 16 at D <= 256 when B * ceil(D/16) work-groups fit the chip
 // (one per CU), else clusters of 8; 8 / 16 force one of the two (the kernels refuse what does not fit).  D > 256: PdShape32.
-// -> 0 / 1 / 2 (PdShape8 / 16 / 32) or -1; fills units, ksplit, kd, mc, P.
+// -> shape 0 / 1 / 2 (PdShape8 / 16 / 32) with its constants and P.
 struct PdPick { int shape, UNITS, KSPLIT, KD, MC, AWS, P; };
+template <class SH>
+static inline void pd_fill(PdPick& k, int shape, int D) {
+    k.shape = shape; k.UNITS = SH::UNITS; k.KSPLIT = SH::KSPLIT; k.KD = SH::KD; k.MC = SH::MC; k.AWS = SH::AWS;
+    k.P = (D + SH::UNITS - 1) / SH::UNITS;
+}
 static inline bool pd_pick(int B, int D, int M, PdPick& k, bool allow16 = true) {
-    auto set = [&](int shape, int U, int KD, int MC, int AWS) {
-        k.shape = shape; k.UNITS = U; k.KSPLIT = PD_THREADS / U; k.KD = KD; k.MC = MC; k.AWS = AWS; k.P = (D + U - 1) / U;
-        return M <= k.P * MC * U && k.P <= PD_MAXP && B * k.P <= lvsr_max_cluster_wgs();
-    };
+    auto fits = [&]() { return M <= k.P * k.MC * k.UNITS && k.P <= PD_MAXP && B * k.P <= lvsr_max_cluster_wgs(); };
     if (D > PdShape32::DMAX) return false;
-    if (D > PdShape8::DMAX) return set(2, PdShape32::UNITS, PdShape32::KD, PdShape32::MC, PdShape32::AWS);
+    if (D > PdShape8::DMAX) { pd_fill<PdShape32>(k, 2, D); return fits(); }
     const int want = lvsr_knob(LVSR_KNOB_DEC_CLUSTER);
-    if (want != 8 && allow16 && set(1, PdShape16::UNITS, PdShape16::KD, PdShape16::MC, PdShape16::AWS)) return true;
+    if (want != 8 && allow16) {
+        pd_fill<PdShape16>(k, 1, D);
+        if (fits()) return true;
+    }
     if (want == 16) return false;          // (allow16 = false: the caller found that clusters of 16 do not fit its LDS budget)
-    return set(0, PdShape8::UNITS, PdShape8::KD, PdShape8::MC, PdShape8::AWS);
+    pd_fill<PdShape8>(k, 0, D);
+    return fits();
 }
 
 // Utterances per launch.  All of them when their clusters fit the chip at once; otherwise — when nothing couples the utterances of a
@@ -68,6 +79,63 @@ static inline bool pd_pick_passes(int B, int D, int M, bool independent, PdPick&
     return false;
 }
 
+// filter-count instantiation of the kernels that serves K filters (-1: none)
+static inline int pd_kc(int K) {
+    const int inst[4] = {0, 4, 10, 16};
+    for (int i = 0; i < 4; ++i)
+        if (K <= inst[i]) return inst[i];
+    return -1;
+}
+
+// What PdGeom (forward) and PbGeom (backward) have in common: eligibility, the filter-count instantiation, the cluster shape `k` and the
+// utterances per launch, own / padded positions per work-group, the row stride of the transposed context table, the phase-clock knob.
+// stack: the two-layer launches (two clusters of 8, PdShape8, per utterance; no passes).  Each file adds its limits, its LDS offsets
+// and the retry with clusters of 8 (allow16 = false) when clusters of 16 do not fit them.
+template <class G>
+static inline bool pd_geom_common(const AttDec& a, G& g, PdPick& k, bool allow16, bool stack) {
+    if ((a.phases & 3) != 3 || a.step_dev != nullptr || a.group_rows != 0) return false;
+    if (a.M > PD_MAXV || a.Tp > PD_MAXV) return false;
+    g.KC = pd_kc(a.K);
+    if (g.KC < 0) return false;
+    g.KCP = (g.KC + 3) / 4 * 4;
+    if (stack) {
+        if (a.D > PdShape8::DMAX) return false;
+        pd_fill<PdShape8>(k, 0, a.D);
+        if (a.M > k.P * k.MC * k.UNITS || a.B * 2 * k.P > lvsr_max_cluster_wgs()) return false;
+        g.nb = a.B;
+    } else if (!pd_pick_passes(a.B, a.D, a.M, a.K == 0 || a.prior_type == 0, k, g.nb, allow16)) return false;
+    g.b0 = 0;
+    g.P = k.P; g.shape = k.shape;
+    g.nown = (a.Tp + g.P - 1) / g.P;
+    g.nownp = (g.nown + PD_CH - 1) / PD_CH * PD_CH;
+    g.FW = 2 * a.c + 1;
+    g.RL = (g.nown + 3) / 4 * 4;
+    if (g.RL % 32 == 0) g.RL += 4;          // transposed table [m][RL] of the MFMA energy path: row stride off the bank period
+    g.prof = lvsr_knob(LVSR_KNOB_PHASE_CLOCK);         // phase clock of work-group 0 (tools/probe_decoder_persist.py); costs ~1 us per label
+    return true;
+}
+
+// The argument block of a *_ws_bytes / *_clusters query: false = answer 0 (no block, or a size that is not positive)
+static inline bool pd_query_args(const lvsr_attdec_args* args, AttDec& a) {
+    if (args == nullptr) return false;
+    memcpy(&a, args, sizeof(a));
+    return !(a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0);
+}
+
+// f(std::integral_constant<int, KC>(), SH()) for the kernels' filter-count instantiation KC and cluster shape: the shape a geometry
+// picked (0 / 1 / 2), or — the two-layer launches — the one shape SH they are built for
+template <class SH, class F>
+static inline void pd_dispatch(int KC, F&& f) {
+    lvsr_dispatch<0, 4, 10, 16>(KC, [&](auto kc) { f(kc, SH()); });
+}
+template <class F>
+static inline void pd_dispatch(int KC, int shape, F&& f) {
+    if (shape == 0) pd_dispatch<PdShape8>(KC, f);
+    else if (shape == 1) pd_dispatch<PdShape16>(KC, f);
+    else pd_dispatch<PdShape32>(KC, f);
+}
+
+// ---- device side ----------------------------------------------------------------------------------------------------------------
 __host__ __device__ __forceinline__ int pd_slot(int k, int KX) { return (k / KX) * (KX + 4) + (k % KX); }
 
 // Window of label i (attdec_window) with the window centres taken from LDS: the centres of ALL utterances bound the window

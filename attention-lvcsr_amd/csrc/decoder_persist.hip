@@ -41,39 +41,21 @@ struct PdGeom {
     int nb, b0;          // utterances of this launch: [b0, b0 + nb) (pd_pick_passes)
 };
 
-
-static int pd_kc(int K) {
-    const int inst[4] = {0, 4, 10, 16};
-    for (int i = 0; i < 4; ++i)
-        if (K <= inst[i]) return inst[i];
-    return -1;
+// The granule planes of a launch (behind the 256-byte header of the workspace): per utterance SW | EN | RS | S (two-layer launch: + SW1 |
+// RS1 | S1 of the layer-1 cluster), then the window centres [2][Bp] and PD_MAXP XCC_ID granules per utterance.  The kernels address
+// them with pd_utt_granules, the query sizes and the launch clears them with pd_planes_bytes.
+__host__ __device__ constexpr int pd_utt_granules(bool stack) { return (stack ? PD_NPLANE_STACK : PD_NPLANE) * PD_MAXV; }
+static size_t pd_planes_bytes(const AttDec& a, const PdGeom& g, bool stack) {
+    return ((size_t)a.B * pd_utt_granules(stack) + 2 * g.Bp + (size_t)a.B * PD_MAXP) * 8;
 }
 
 // stack: the two-layer launch (lvsr_attdec_fwd_persistent_stack2): clusters of 8 (PdShape8), two of them per utterance
 static bool pd_geom(const AttDec& a, PdGeom& g, bool allow16 = true, bool stack = false) {
-    if ((a.phases & 3) != 3 || a.step_dev != nullptr || a.group_rows != 0) return false;
-    if (a.M > PD_MAXV || a.Tp > PD_MAXV) return false;
-    g.KC = pd_kc(a.K);
-    if (g.KC < 0) return false;
-    g.KCP = (g.KC + 3) / 4 * 4;
     PdPick k;
-    if (stack) {
-        if (a.D > PdShape8::DMAX) return false;
-        k.shape = 0; k.UNITS = PdShape8::UNITS; k.KSPLIT = PdShape8::KSPLIT; k.KD = PdShape8::KD; k.MC = PdShape8::MC; k.AWS = PdShape8::AWS;
-        k.P = (a.D + k.UNITS - 1) / k.UNITS;
-        if (a.M > k.P * k.MC * k.UNITS || a.B * 2 * k.P > lvsr_max_cluster_wgs()) return false;
-    } else if (!pd_pick_passes(a.B, a.D, a.M, a.K == 0 || a.prior_type == 0, k, g.nb, allow16)) return false;
-    if (stack) g.nb = a.B;
-    g.b0 = 0;
-    g.P = k.P; g.shape = k.shape;
-    g.nown = (a.Tp + g.P - 1) / g.P;
-    g.nownp = (g.nown + PD_CH - 1) / PD_CH * PD_CH;
-    g.FW = 2 * a.c + 1;
+    if (!pd_geom_common(a, g, k, allow16, stack)) return false;
     if (a.K > 0 && g.FW > 4 * 8 * PD_NW) return false;          // tap groups of the convolution: 8 per wave
     int o = 0;
     auto take = [&](int n) { const int at = o; o += (n + 3) / 4 * 4; return at; };
-    g.RL = (g.nown + 3) / 4 * 4;
-    if (g.RL % 32 == 0) g.RL += 4;          // transposed table [m][RL] of the MFMA energy path: row stride off the bank period
     g.o_pa = take((g.KC > 0 ? g.RL : g.nown) * a.M + 64);
     g.o_a = take(a.Tp * k.AWS);
     g.o_cv = take(g.nownp * (g.KCP > 0 ? g.KCP : 4));
@@ -91,7 +73,6 @@ static bool pd_geom(const AttDec& a, PdGeom& g, bool allow16 = true, bool stack 
     g.o_clk = take(2 * (PD_NPROF + 1));
     g.o_cp = take(PD_NW * 16 * 17);
     g.total = o;
-    g.prof = lvsr_knob(LVSR_KNOB_PHASE_CLOCK);         // phase clock of work-group 0 (tools/probe_decoder_persist.py); costs ~1 us per label
     if (o > PD_LDS_FLOATS && k.shape == 1 && allow16 && !stack) return pd_geom(a, g, false);      // clusters of 8 instead, if they fit
     return o <= PD_LDS_FLOATS;
 }
@@ -163,13 +144,13 @@ __device__ __forceinline__ void pd_stack_layer1(const AttDec& a, const PdGeom& g
     for (int t = tid; t < Tp; t += PD_THREADS) al[t] = a.W[(size_t)b * Tp + t];
     for (int k = tid; k < D; k += PD_THREADS) sv[pd_slot(k, PD_KD)] = a.S[(size_t)b * SLD + D + k];
     float sj = junit ? a.S[(size_t)b * SLD + D + j] : 0.f;
-    u64* const base = planes + (size_t)b * PD_NPLANE_STACK * PD_MAXV;
+    u64* const base = planes + (size_t)b * pd_utt_granules(true);
     u64* const gEN = base + PD_MAXV;
     u64* const gS0 = base + 3 * PD_MAXV;
     u64* const gSW1 = base + 4 * PD_MAXV;
     u64* const gRS1 = base + 5 * PD_MAXV;
     u64* const gS1 = base + 6 * PD_MAXV;
-    u64* const gPOS = planes + (size_t)B * PD_NPLANE_STACK * PD_MAXV;
+    u64* const gPOS = planes + (size_t)B * pd_utt_granules(true);
     const bool plain = cluster_shares_xcd(gPOS + 2 * g.Bp + (size_t)b * PD_MAXP, 2 * P, P + p, abort_word);
     const bool winprior = K > 0 && a.prior_type != 0;
     __syncthreads();
@@ -447,13 +428,12 @@ __global__ __launch_bounds__(PD_THREADS) void attdec_pfwd_kernel(AttDec a, lvsr_
     for (int t = tid; t < Tp; t += PD_THREADS) al[t] = a.W[(size_t)b * Tp + t];
     for (int k = tid; k < D; k += PD_THREADS) sv[pd_slot(k, PD_KD)] = a.S[(size_t)b * SLD + k];
     float sj = junit ? a.S[(size_t)b * SLD + j] : 0.f;
-    constexpr int NPL = STACK ? PD_NPLANE_STACK : PD_NPLANE;
-    u64* const gSW = planes + (size_t)b * NPL * PD_MAXV;
+    u64* const gSW = planes + (size_t)b * pd_utt_granules(STACK);
     u64* const gEN = gSW + PD_MAXV;
     u64* const gRS = gSW + 2 * PD_MAXV;
     u64* const gS = gSW + 3 * PD_MAXV;
     u64* const gSW1 = gSW + 4 * PD_MAXV;                             // (two-layer launch) layer 1's part of the transformed state
-    u64* const gPOS = planes + (size_t)B * NPL * PD_MAXV;            // [2][Bp], shared by all clusters
+    u64* const gPOS = planes + (size_t)B * pd_utt_granules(STACK);           // [2][Bp], shared by all clusters
     // plain stores for the exchanges INSIDE the cluster when its work-groups share an XCD (persist.h); the window centres travel
     // between clusters and stay write-through.  The XCC_ID granules: PD_MAXP per utterance behind the window centres.
     const bool plain = cluster_shares_xcd(gPOS + 2 * g.Bp + (size_t)b * PD_MAXP, STACK ? 2 * P : P, p, abort_word);
@@ -885,12 +865,10 @@ extern "C" int lvsr_attdec_glimpses(void* stream, const lvsr_attdec_args* args) 
 }
 
 extern "C" long long lvsr_attdec_persist_ws_bytes(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PdGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pd_geom(a, g)) return 0;
-    return 256 + ((long long)a.B * PD_NPLANE * PD_MAXV + 2 * g.Bp + (long long)a.B * PD_MAXP) * 8;
+    if (!pd_query_args(args, a) || !pd_geom(a, g)) return 0;
+    return 256 + (long long)pd_planes_bytes(a, g, false);
 }
 
 extern "C" int lvsr_attdec_fwd_persistent(void* stream, const lvsr_attdec_args* args, const lvsr_attdec_plain* plain, void* ws,
@@ -908,28 +886,17 @@ extern "C" int lvsr_attdec_fwd_persistent(void* stream, const lvsr_attdec_args* 
     hipStream_t s = (hipStream_t)stream;
     int* ab = (int*)ws;
     u64* planes = (u64*)((char*)ws + 256);
-    const size_t bytes = ((size_t)a.B * PD_NPLANE * PD_MAXV + 2 * g.Bp + (size_t)a.B * PD_MAXP) * 8;
     auto enqueue = [&]() {
-        (void)hipMemsetAsync(planes, 0, bytes, s);          // the abort word in front of the planes is sticky: cleared by the host only
+        (void)hipMemsetAsync(planes, 0, pd_planes_bytes(a, g, false), s);          // the abort word in front of the planes is sticky: cleared by the host only
         const dim3 block(PD_THREADS);
         PdGeom gp = g;
         for (gp.b0 = 0; gp.b0 < a.B; gp.b0 += g.nb) {
-        gp.nb = min(g.nb, a.B - gp.b0);
-        const dim3 grid(cluster_grid(gp.nb, g.P, 0));
-#define PD_LAUNCH(KCV, SHAPE) hipLaunchKernelGGL((attdec_pfwd_kernel<KCV, SHAPE, false>), grid, block, 0, s, a, w, gp, planes, ab, PdStack())
-#define PD_LAUNCH_KC(SHAPE)                       \
-        switch (g.KC) {                           \
-            case 0: PD_LAUNCH(0, SHAPE); break;   \
-            case 4: PD_LAUNCH(4, SHAPE); break;   \
-            case 10: PD_LAUNCH(10, SHAPE); break; \
-            default: PD_LAUNCH(16, SHAPE); break; \
+            gp.nb = min(g.nb, a.B - gp.b0);
+            const dim3 grid(cluster_grid(gp.nb, g.P, 0));
+            pd_dispatch(g.KC, g.shape, [&](auto kc, auto sh) {
+                hipLaunchKernelGGL((attdec_pfwd_kernel<decltype(kc)::value, decltype(sh), false>), grid, block, 0, s, a, w, gp, planes, ab, PdStack());
+            });
         }
-        if (g.shape == 0) { PD_LAUNCH_KC(PdShape8) }
-        else if (g.shape == 1) { PD_LAUNCH_KC(PdShape16) }
-        else { PD_LAUNCH_KC(PdShape32) }
-        }
-#undef PD_LAUNCH_KC
-#undef PD_LAUNCH
     };
     GraphKey key("attdec_pfwd");
     key.add(&a, sizeof(a));
@@ -941,12 +908,10 @@ extern "C" int lvsr_attdec_fwd_persistent(void* stream, const lvsr_attdec_args* 
 }
 
 extern "C" long long lvsr_attdec_stack2_persist_ws_bytes(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PdGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pd_geom(a, g, false, true)) return 0;
-    return 256 + ((long long)a.B * PD_NPLANE_STACK * PD_MAXV + 2 * g.Bp + (long long)a.B * PD_MAXP) * 8;
+    if (!pd_query_args(args, a) || !pd_geom(a, g, false, true)) return 0;
+    return 256 + (long long)pd_planes_bytes(a, g, true);
 }
 
 extern "C" int lvsr_attdec_fwd_persistent_stack2(void* stream, const lvsr_attdec_args* args, const lvsr_attdec_plain* plain,
@@ -967,16 +932,12 @@ extern "C" int lvsr_attdec_fwd_persistent_stack2(void* stream, const lvsr_attdec
     hipStream_t s = (hipStream_t)stream;
     int* ab = (int*)ws;
     u64* planes = (u64*)((char*)ws + 256);
-    const size_t bytes = ((size_t)a.B * PD_NPLANE_STACK * PD_MAXV + 2 * g.Bp + (size_t)a.B * PD_MAXP) * 8;
     auto enqueue = [&]() {
-        (void)hipMemsetAsync(planes, 0, bytes, s);
+        (void)hipMemsetAsync(planes, 0, pd_planes_bytes(a, g, true), s);
         const dim3 grid(cluster_grid(a.B, 2 * g.P, 0)), block(PD_THREADS);
-        switch (g.KC) {
-            case 0: hipLaunchKernelGGL((attdec_pfwd_kernel<0, PdShape8, true>), grid, block, 0, s, a, w, g, planes, ab, k2); break;
-            case 4: hipLaunchKernelGGL((attdec_pfwd_kernel<4, PdShape8, true>), grid, block, 0, s, a, w, g, planes, ab, k2); break;
-            case 10: hipLaunchKernelGGL((attdec_pfwd_kernel<10, PdShape8, true>), grid, block, 0, s, a, w, g, planes, ab, k2); break;
-            default: hipLaunchKernelGGL((attdec_pfwd_kernel<16, PdShape8, true>), grid, block, 0, s, a, w, g, planes, ab, k2); break;
-        }
+        pd_dispatch<PdShape8>(g.KC, [&](auto kc, auto sh) {
+            hipLaunchKernelGGL((attdec_pfwd_kernel<decltype(kc)::value, decltype(sh), true>), grid, block, 0, s, a, w, g, planes, ab, k2);
+        });
     };
     GraphKey key("attdec_pfwd_stack2");
     key.add(&a, sizeof(a));

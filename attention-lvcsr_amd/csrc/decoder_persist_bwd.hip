@@ -43,40 +43,23 @@ struct PbGeom {
     int nb, b0;          // utterances of this launch: [b0, b0 + nb) (pd_pick_passes)
 };
 
-static int pb_kc(int K) {
-    const int inst[4] = {0, 4, 10, 16};
-    for (int i = 0; i < 4; ++i)
-        if (K <= inst[i]) return inst[i];
-    return -1;
+// Granules of an utterance's planes, P work-groups per cluster (the kernels' stride), and the bytes of a launch's planes (behind the
+// 256-byte header of the workspace: what the query sizes and the launch clears)
+__host__ __device__ constexpr size_t pb_utt_granules(bool stack, int P) {
+    return stack ? PB_SMALL + PB_STACK_EXTRA + (size_t)P * PB_PERWG_STACK : PB_SMALL + (size_t)P * PB_PERWG;
 }
+static size_t pb_planes_bytes(const AttDec& a, const PbGeom& g, bool stack) { return (size_t)a.B * pb_utt_granules(stack, g.P) * 8; }
 
 static bool pb_geom(const AttDec& a, PbGeom& g, bool allow16 = true, bool stack = false) {
-    if ((a.phases & 3) != 3 || a.step_dev != nullptr || a.group_rows != 0) return false;
-    if (a.M > PD_MAXV || a.Tp > PD_MAXV) return false;
-    g.KC = pb_kc(a.K);
-    if (g.KC < 0) return false;
-    g.KCP = (g.KC + 3) / 4 * 4;
+    if (stack && (3 * a.D) % 4 != 0) return false;
     PdPick k;
-    if (stack) {          // two clusters of 8 per utterance (PdShape8)
-        if (a.D > PdShape8::DMAX || (3 * a.D) % 4 != 0) return false;
-        k.shape = 0; k.UNITS = PdShape8::UNITS; k.KSPLIT = PdShape8::KSPLIT; k.KD = PdShape8::KD; k.MC = PdShape8::MC; k.AWS = PdShape8::AWS;
-        k.P = (a.D + k.UNITS - 1) / k.UNITS;
-        if (a.M > k.P * k.MC * k.UNITS || a.B * 2 * k.P > lvsr_max_cluster_wgs()) return false;
-    } else if (!pd_pick_passes(a.B, a.D, a.M, a.K == 0 || a.prior_type == 0, k, g.nb, allow16)) return false;
-    if (stack) g.nb = a.B;
-    g.b0 = 0;
-    g.P = k.P; g.shape = k.shape;
+    if (!pd_geom_common(a, g, k, allow16, stack)) return false;
     const int DP = k.KSPLIT * k.KD > 256 ? 512 : 256, MS = k.MC * k.UNITS;      // padded decoder width of the exchanges, match columns per work-group
-    g.nown = (a.Tp + g.P - 1) / g.P;
-    g.nownp = (g.nown + PD_CH - 1) / PD_CH * PD_CH;
     // the q phase maps one lane group (16 lanes at D <= 256, 32 above) per own position, the alignment-gradient gather one granule
     // row of NTL positions per source work-group (P NTL <= 512 threads)
     if (g.nown > (DP == 256 ? 32 : 16)) return allow16 && k.shape == 1 && !stack ? pb_geom(a, g, false) : false;
     g.NTL = (g.nown <= 16 || DP == 512) ? 16 : 32;
     if (g.P * g.NTL > PD_THREADS) return false;
-    g.FW = 2 * a.c + 1;
-    g.RL = (g.nown + 3) / 4 * 4;
-    if (g.RL % 32 == 0) g.RL += 4;
     int o = 0;
     auto take = [&](int n) { const int at = o; o += (n + 3) / 4 * 4; return at; };
     g.o_pa = take(g.RL * a.M + 64);
@@ -119,7 +102,6 @@ static bool pb_geom(const AttDec& a, PbGeom& g, bool allow16 = true, bool stack 
     g.o_dpa = g.DPAL ? take(g.nown * g.DPS) : 0;
     g.YMD = (lvsr_knob(LVSR_KNOB_PERSIST_FLAGS) & PF_NOYMPRE) != 0;
     g.total = o;
-    g.prof = lvsr_knob(LVSR_KNOB_PHASE_CLOCK);
     if (o > PD_LDS_FLOATS && k.shape == 1 && allow16 && !stack) return pb_geom(a, g, false);      // clusters of 8 instead, if they fit
     return o <= PD_LDS_FLOATS;
 }
@@ -392,7 +374,7 @@ __global__ __launch_bounds__(PD_THREADS) void attdec_pbwd_kernel(AttBwd gb, lvsr
     int b, p;
     if (!cluster_of_block(STACK ? 2 * P : P, g.nb, 0, b, p)) return;  // (work-groups of the grid's padding)
     b += g.b0;
-    u64* const gA = planes + (size_t)b * (STACK ? PB_SMALL + PB_STACK_EXTRA + (size_t)P * PB_PERWG_STACK : PB_SMALL + (size_t)P * PB_PERWG);
+    u64* const gA = planes + (size_t)b * pb_utt_granules(STACK, P);
     if (STACK && p >= P) {            // the second cluster of the utterance: layer 1 of the stack
         pb_stack_layer1<SH>(gb, g, k2, lds, gA, abort_word, b, p - P);
         return;
@@ -998,21 +980,28 @@ __global__ __launch_bounds__(PD_THREADS) void attdec_pbwd_kernel(AttBwd gb, lvsr
     }
 }
 
+// What both reverse walks ask of their arguments beyond their own state layouts; `who`: the entry point called
+static int pb_check_args(const AttBwd& gb, const lvsr_attdec_plain& w, const char* who) {
+    const AttDec& a = gb.f;
+    LVSR_REQUIRE(a.PA_bs == a.M && a.PA_ts == (long long)a.B * a.M, "%s: contexts must be contiguous (Tp,B,*)", who);
+    LVSR_REQUIRE(w.Ws && w.Whg && w.Whh && w.AW && gb.QR && gb.DXG && gb.DSW && gb.dPA && gb.ds && gb.accWe,
+                 "%s: missing buffers (AW, QR and the plain weights of the attention / layer-0 block are required)", who);
+    LVSR_REQUIRE(a.K == 0 || (gb.DCV && gb.accH), "%s: DCV / accH missing", who);
+    return LVSR_OK;
+}
+static bool pb_rows_aligned(int ld, int D) { return (ld ? ld : 3 * D) % 4 == 0; }
+
 extern "C" long long lvsr_attdec_bwd_persist_ws_bytes(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PbGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pb_geom(a, g)) return 0;
-    return 256 + (long long)a.B * (PB_SMALL + (long long)g.P * PB_PERWG) * 8;
+    if (!pd_query_args(args, a) || !pb_geom(a, g)) return 0;
+    return 256 + (long long)pb_planes_bytes(a, g, false);
 }
 
 extern "C" int lvsr_attdec_bwd_persist_clusters(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PbGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pb_geom(a, g)) return 0;
+    if (!pd_query_args(args, a) || !pb_geom(a, g)) return 0;
     return g.P;
 }
 
@@ -1025,57 +1014,39 @@ extern "C" int lvsr_attdec_bwd_persistent(void* stream, const lvsr_attdec_bwd_ar
     LVSR_REQUIRE(a.label0 == 0 && (args->parts & 3) % 3 == 0 && (a.S_ld == 0 || a.S_ld == a.D) && (args->ds_ld == 0 || args->ds_ld == a.D),
                  "lvsr_attdec_bwd_persistent: runs all labels and all parts on contiguous states");
     PbGeom g;
-    LVSR_REQUIRE((plain->AW_ld ? plain->AW_ld : 3 * a.D) % 4 == 0 && (plain->AW_ld == 0 || plain->AW_ld >= 3 * a.D),
+    LVSR_REQUIRE(pb_rows_aligned(plain->AW_ld, a.D) && (plain->AW_ld == 0 || plain->AW_ld >= 3 * a.D),
                  "lvsr_attdec_bwd_persistent: the rows of AW must be a multiple of 4 floats apart (pad them: AW_ld)");
     LVSR_REQUIRE(pb_geom(a, g), "lvsr_attdec_bwd_persistent: configuration outside the persistent kernel's limits "
                  "(lvsr_attdec_bwd_persist_ws_bytes returns 0 for it)");
-    LVSR_REQUIRE(a.PA_bs == a.M && a.PA_ts == (long long)a.B * a.M, "lvsr_attdec_bwd_persistent: contexts must be contiguous (Tp,B,*)");
-    LVSR_REQUIRE(plain->Ws && plain->Whg && plain->Whh && plain->AW && gb.QR && gb.DXG && gb.DSW && gb.dPA && gb.ds && gb.accWe,
-                 "lvsr_attdec_bwd_persistent: missing buffers (AW, QR and the plain weights are required)");
-    LVSR_REQUIRE(a.K == 0 || (gb.DCV && gb.accH), "lvsr_attdec_bwd_persistent: DCV / accH missing");
+    if (int rc = pb_check_args(gb, *plain, "lvsr_attdec_bwd_persistent")) return rc;
     const lvsr_attdec_plain w = *plain;
     hipStream_t s = (hipStream_t)stream;
     int* ab = (int*)ws;
     u64* planes = (u64*)((char*)ws + 256);
-    const size_t bytes = (size_t)a.B * (PB_SMALL + (size_t)g.P * PB_PERWG) * 8;
-    (void)hipMemsetAsync(planes, 0, bytes, s);          // the abort word in front of the planes is sticky: cleared by the host only
+    (void)hipMemsetAsync(planes, 0, pb_planes_bytes(a, g, false), s);          // the abort word in front of the planes is sticky: cleared by the host only
     const dim3 block(PD_THREADS);
     PbGeom gp = g;
     for (gp.b0 = 0; gp.b0 < a.B; gp.b0 += g.nb) {
-    gp.nb = min(g.nb, a.B - gp.b0);
-    const dim3 grid(cluster_grid(gp.nb, g.P, 0));
-#define PB_LAUNCH(KCV, SHAPE) hipLaunchKernelGGL((attdec_pbwd_kernel<KCV, SHAPE, false>), grid, block, 0, s, gb, w, gp, planes, ab, PbStack())
-#define PB_LAUNCH_KC(SHAPE)                       \
-    switch (g.KC) {                               \
-        case 0: PB_LAUNCH(0, SHAPE); break;       \
-        case 4: PB_LAUNCH(4, SHAPE); break;       \
-        case 10: PB_LAUNCH(10, SHAPE); break;     \
-        default: PB_LAUNCH(16, SHAPE); break;     \
+        gp.nb = min(g.nb, a.B - gp.b0);
+        const dim3 grid(cluster_grid(gp.nb, g.P, 0));
+        pd_dispatch(g.KC, g.shape, [&](auto kc, auto sh) {
+            hipLaunchKernelGGL((attdec_pbwd_kernel<decltype(kc)::value, decltype(sh), false>), grid, block, 0, s, gb, w, gp, planes, ab, PbStack());
+        });
     }
-    if (g.shape == 0) { PB_LAUNCH_KC(PdShape8) }
-    else if (g.shape == 1) { PB_LAUNCH_KC(PdShape16) }
-    else { PB_LAUNCH_KC(PdShape32) }
-    }
-#undef PB_LAUNCH_KC
-#undef PB_LAUNCH
     return lvsr_check_launch("lvsr_attdec_bwd_persistent");
 }
 
 extern "C" long long lvsr_attdec_stack2_bwd_persist_ws_bytes(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PbGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pb_geom(a, g, false, true)) return 0;
-    return 256 + (long long)a.B * (PB_SMALL + PB_STACK_EXTRA + (long long)g.P * PB_PERWG_STACK) * 8;
+    if (!pd_query_args(args, a) || !pb_geom(a, g, false, true)) return 0;
+    return 256 + (long long)pb_planes_bytes(a, g, true);
 }
 
 extern "C" int lvsr_attdec_stack2_bwd_persist_clusters(const lvsr_attdec_args* args) {
-    if (args == nullptr) return 0;
     AttDec a;
-    memcpy(&a, args, sizeof(a));
     PbGeom g;
-    if (a.Tp <= 0 || a.B <= 0 || a.L <= 0 || a.E <= 0 || a.D <= 0 || a.M <= 0 || a.K < 0 || !pb_geom(a, g, false, true)) return 0;
+    if (!pd_query_args(args, a) || !pb_geom(a, g, false, true)) return 0;
     return g.P;
 }
 
@@ -1089,14 +1060,11 @@ extern "C" int lvsr_attdec_bwd_persistent_stack2(void* stream, const lvsr_attdec
     LVSR_REQUIRE(a.label0 == 0 && (args->parts & 3) % 3 == 0 && a.S_ld >= 2 * a.D && args->ds_ld >= 2 * a.D,
                  "lvsr_attdec_bwd_persistent_stack2: runs all labels; states and state gradients hold both layers side by side (S_ld, ds_ld >= 2 D)");
     PbGeom g;
-    LVSR_REQUIRE((plain->AW_ld ? plain->AW_ld : 3 * a.D) % 4 == 0 && (l1->AW1_ld ? l1->AW1_ld : 3 * a.D) % 4 == 0,
+    LVSR_REQUIRE(pb_rows_aligned(plain->AW_ld, a.D) && pb_rows_aligned(l1->AW1_ld, a.D),
                  "lvsr_attdec_bwd_persistent_stack2: the rows of AW / AW1 must be a multiple of 4 floats apart");
     LVSR_REQUIRE(pb_geom(a, g, false, true), "lvsr_attdec_bwd_persistent_stack2: configuration outside the kernel's limits "
                  "(lvsr_attdec_stack2_bwd_persist_ws_bytes returns 0 for it)");
-    LVSR_REQUIRE(a.PA_bs == a.M && a.PA_ts == (long long)a.B * a.M, "lvsr_attdec_bwd_persistent_stack2: contexts must be contiguous (Tp,B,*)");
-    LVSR_REQUIRE(plain->Ws && plain->Whg && plain->Whh && plain->AW && gb.QR && gb.DXG && gb.DSW && gb.dPA && gb.ds && gb.accWe,
-                 "lvsr_attdec_bwd_persistent_stack2: missing buffers of the attention / layer-0 block");
-    LVSR_REQUIRE(a.K == 0 || (gb.DCV && gb.accH), "lvsr_attdec_bwd_persistent_stack2: DCV / accH missing");
+    if (int rc = pb_check_args(gb, *plain, "lvsr_attdec_bwd_persistent_stack2")) return rc;
     LVSR_REQUIRE(l1->Whg1 && l1->Whh1 && l1->Ws1 && l1->F1 && l1->AW1 && l1->U1 && l1->R1 && l1->C1 && l1->DXG1,
                  "lvsr_attdec_bwd_persistent_stack2: layer-1 block incomplete");
     const lvsr_attdec_plain w = *plain;
@@ -1104,14 +1072,10 @@ extern "C" int lvsr_attdec_bwd_persistent_stack2(void* stream, const lvsr_attdec
     hipStream_t s = (hipStream_t)stream;
     int* ab = (int*)ws;
     u64* planes = (u64*)((char*)ws + 256);
-    const size_t bytes = (size_t)a.B * (PB_SMALL + PB_STACK_EXTRA + (size_t)g.P * PB_PERWG_STACK) * 8;
-    (void)hipMemsetAsync(planes, 0, bytes, s);
+    (void)hipMemsetAsync(planes, 0, pb_planes_bytes(a, g, true), s);
     const dim3 grid(cluster_grid(a.B, 2 * g.P, 0)), block(PD_THREADS);
-    switch (g.KC) {
-        case 0: hipLaunchKernelGGL((attdec_pbwd_kernel<0, PdShape8, true>), grid, block, 0, s, gb, w, g, planes, ab, k2); break;
-        case 4: hipLaunchKernelGGL((attdec_pbwd_kernel<4, PdShape8, true>), grid, block, 0, s, gb, w, g, planes, ab, k2); break;
-        case 10: hipLaunchKernelGGL((attdec_pbwd_kernel<10, PdShape8, true>), grid, block, 0, s, gb, w, g, planes, ab, k2); break;
-        default: hipLaunchKernelGGL((attdec_pbwd_kernel<16, PdShape8, true>), grid, block, 0, s, gb, w, g, planes, ab, k2); break;
-    }
+    pd_dispatch<PdShape8>(g.KC, [&](auto kc, auto sh) {
+        hipLaunchKernelGGL((attdec_pbwd_kernel<decltype(kc)::value, decltype(sh), true>), grid, block, 0, s, gb, w, g, planes, ab, k2);
+    });
     return lvsr_check_launch("lvsr_attdec_bwd_persistent_stack2");
 }

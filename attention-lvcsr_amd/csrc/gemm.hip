@@ -468,10 +468,6 @@ __device__ __forceinline__ void sgemm_tile_kmajor(GemmArgs g, int bx, int by, in
                 }
             }
 }
-template <bool TA, bool TB, bool FAST>
-__device__ __forceinline__ void sgemm128_tile(GemmArgs g, int bx, int by, int bz, bool fast = true) {
-    sgemm_tile<128, 128, TA, TB, FAST>(g, bx, by, bz, fast);
-}
 
 template <bool TA, bool TB, bool FAST>
 __global__ __launch_bounds__(256) void lvsr_sgemm64_kernel(GemmArgs g) {
@@ -485,7 +481,7 @@ __global__ __launch_bounds__(256) void lvsr_sgemm128_kernel(GemmArgs g) {
     // (k-split, m-tile, n-tile) sequence, n fastest
     const int total = gridDim.x * gridDim.y * gridDim.z;
     const int t = gemm_xcd_order(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z), total);
-    sgemm128_tile<TA, TB, FAST>(g, t % gridDim.x, (t / gridDim.x) % gridDim.y, t / (gridDim.x * gridDim.y));
+    sgemm_tile<128, 128, TA, TB, FAST>(g, t % gridDim.x, (t / gridDim.x) % gridDim.y, t / (gridDim.x * gridDim.y));
 }
 
 // ---- grouped launch of transposed-A products (weight gradients): C_p = A_p^T B_p (+ beta_p C_p) for up to GROUP_MAX problems.
@@ -522,7 +518,7 @@ __global__ __launch_bounds__(256) void lvsr_sgemm128_grouped_tn_kernel(GroupPack
     g.M = d.M; g.N = d.N; g.K = d.K; g.lda = d.lda; g.ldb = d.ldb; g.ldc = d.ldc; g.transA = 1; g.transB = 0;
     g.alpha = 1.f; g.beta = d.beta; g.ksplit = d.ksplit; g.kchunk = d.kchunk; g.part = pk.part + d.part_off;
     g.batch = 1; g.sA = g.sB = g.sC = 0;
-    sgemm128_tile<true, false, true>(g, local % d.gx, (local / d.gx) % d.gy, local / (d.gx * d.gy), d.fast != 0);
+    sgemm_tile<128, 128, true, false, true>(g, local % d.gx, (local / d.gx) % d.gy, local / (d.gx * d.gy), d.fast != 0);
 }
 
 // The fold: FOLD_ELEMS outputs of one problem per work-group, four per thread (one float4 where N, ldc and the addresses allow,
@@ -743,6 +739,25 @@ __global__ __launch_bounds__(256) void lvsr_pack_b_kernel(const float* W, int ld
     }
 }
 
+// ---- host-side plan pieces that more than one launch uses ----------------------------------------------------------------------------
+// 16-byte vector loads of both operands: rows a multiple of 4 floats apart from 16-byte aligned bases (else the guarded scalar loads)
+static bool operands_aligned(const float* A, int lda, const float* B, int ldb) {
+    return (lda & 3) == 0 && (ldb & 3) == 0 && (((size_t)A) & 15) == 0 && (((size_t)B) & 15) == 0;
+}
+
+// Row split of a column sum over M x N: ~256 rows per slice, at most ~1024 work-groups, and partials that fit the workspace (no
+// workspace, or fewer than 512 rows: one slice).  lvsr_colsum and lvsr_colsum_many both cut here, so a sum gives the same bits alone
+// and as a member.
+static int colsum_split(int M, int N, bool have_ws, long long ws_bytes) {
+    if (!have_ws || M < 512) return 1;
+    const int nx = (N + 63) / 64;
+    int S = (M + 255) / 256;
+    const int want = (1024 + nx - 1) / nx;          // aim at ~1024 work-groups
+    if (S > want) S = want;
+    while (S > 1 && (long long)S * N * 4 > ws_bytes) --S;
+    return S;
+}
+
 extern "C" {
 
 static int sgemm_launch(void* stream, int transA, int transB, int M, int N, int K, float alpha, const float* A, int lda,
@@ -795,29 +810,12 @@ static int sgemm_launch(void* stream, int transA, int transB, int M, int N, int 
     if (!big) {
         hipLaunchKernelGGL(lvsr_sgemm_kernel, grid, dim3(256), 0, st, g);
     } else {
-        const bool fast = (lda & 3) == 0 && (ldb & 3) == 0 && (((size_t)A) & 15) == 0 && (((size_t)B) & 15) == 0 &&
-                          (batch == 1 || ((sA & 3) == 0 && (sB & 3) == 0));
-#define LVSR_GEMM128(TA_, TB_)                                                                              \
-    do {                                                                                                    \
-        if (fast) hipLaunchKernelGGL((lvsr_sgemm128_kernel<TA_, TB_, true>), grid, dim3(256), 0, st, g);    \
-        else hipLaunchKernelGGL((lvsr_sgemm128_kernel<TA_, TB_, false>), grid, dim3(256), 0, st, g);        \
-    } while (0)
-#define LVSR_GEMM64(TA_, TB_)                                                                               \
-    do {                                                                                                    \
-        if (fast) hipLaunchKernelGGL((lvsr_sgemm64_kernel<TA_, TB_, true>), grid, dim3(256), 0, st, g);     \
-        else hipLaunchKernelGGL((lvsr_sgemm64_kernel<TA_, TB_, false>), grid, dim3(256), 0, st, g);         \
-    } while (0)
-        if (mid) {
-            if (!transA && !transB) LVSR_GEMM64(false, false);
-            else if (transA && !transB) LVSR_GEMM64(true, false);
-            else if (!transA && transB) LVSR_GEMM64(false, true);
-            else LVSR_GEMM64(true, true);
-        } else if (!transA && !transB) LVSR_GEMM128(false, false);
-        else if (transA && !transB) LVSR_GEMM128(true, false);
-        else if (!transA && transB) LVSR_GEMM128(false, true);
-        else LVSR_GEMM128(true, true);
-#undef LVSR_GEMM128
-#undef LVSR_GEMM64
+        const bool fast = operands_aligned(A, lda, B, ldb) && (batch == 1 || ((sA & 3) == 0 && (sB & 3) == 0));
+        lvsr_dispatch<0, 1, 2, 3, 4, 5, 6, 7>((transA ? 4 : 0) | (transB ? 2 : 0) | (fast ? 1 : 0), [&](auto v) {
+            constexpr bool TA = (decltype(v)::value & 4) != 0, TB = (decltype(v)::value & 2) != 0, FAST = (decltype(v)::value & 1) != 0;
+            if (mid) hipLaunchKernelGGL((lvsr_sgemm64_kernel<TA, TB, FAST>), grid, dim3(256), 0, st, g);
+            else hipLaunchKernelGGL((lvsr_sgemm128_kernel<TA, TB, FAST>), grid, dim3(256), 0, st, g);
+        });
     }
     if (g.ksplit > 1) {
         int nb = (int)(((size_t)M * N + 255) / 256);
@@ -848,9 +846,7 @@ int lvsr_sgemm_batched(void* stream, int transA, int transB, int M, int N, int K
 // one chunk per tile.  The chunk boundaries fix the order of every sum, so the cut is a function of K and the workspace size alone:
 // per-member depths that balance the launch change the last bits of the gradients, and a training run does not forgive that
 // (DESIGN.md section 3.3).  What the launch is free to choose is where its units run — group_order.
-static bool group_aligned(const lvsr_gemm_desc& s) {
-    return (s.lda & 3) == 0 && (s.ldb & 3) == 0 && (((size_t)s.A) & 15) == 0 && (((size_t)s.B) & 15) == 0;
-}
+static bool group_aligned(const lvsr_gemm_desc& s) { return operands_aligned(s.A, s.lda, s.B, s.ldb); }
 static void group_cut(const lvsr_gemm_desc* s, int n, long long ws_bytes, int* ksplit, int* kchunk) {
     int target = 1024;
     if (ws_bytes > 0) {
@@ -937,13 +933,7 @@ int lvsr_colsum(void* stream, const float* X, int M, int N, int ldx, float* out,
                 long long ws_bytes) {
     if (N <= 0) return LVSR_OK;
     const int nx = (N + 63) / 64;
-    int S = 1;
-    if (ws && M >= 512) {
-        S = (M + 255) / 256;
-        const int want = (1024 + nx - 1) / nx;          // aim at ~1024 work-groups
-        if (S > want) S = want;
-        while (S > 1 && (long long)S * N * 4 > ws_bytes) --S;
-    }
+    const int S = colsum_split(M, N, ws != nullptr, ws_bytes);
     const int rows_per = (M + S - 1) / S;
     hipLaunchKernelGGL(lvsr_colsum_kernel, dim3(nx, S), dim3(256), 0, (hipStream_t)stream, X, M, N, ldx, out, beta, rows_per,
                        S > 1 ? ws : nullptr);
@@ -967,13 +957,7 @@ int lvsr_colsum_many(void* stream, const lvsr_colsum_desc* descs, int n, float* 
             ColsumMember& c = pk.m[i];
             c.X = d.X; c.out = d.out; c.M = d.M; c.N = d.N; c.ldx = d.ldx; c.beta = d.beta;
             c.nx = (d.N + 63) / 64;
-            int S = 1;                                      // the split lvsr_colsum makes, from the workspace IT would have been given
-            if (ws && d.M >= 512) {
-                S = (d.M + 255) / 256;
-                const int want = (1024 + c.nx - 1) / c.nx;
-                if (S > want) S = want;
-                while (S > 1 && (long long)S * d.N * 4 > split_ws_bytes) --S;
-            }
+            const int S = colsum_split(d.M, d.N, ws != nullptr, split_ws_bytes);      // (from the workspace lvsr_colsum would have been given)
             c.S = S;
             c.rows_per = (d.M + S - 1) / S;
             c.part = ws ? ws + off : nullptr;
