@@ -1,6 +1,7 @@
 // Training and validation observables of the reference's train() (lvsr/main.py:317-396, 526-569; lvsr/expressions.py:14-25) as
 // reductions on the device: the alignment penalty and entropy, min / max / mean |x| of a tensor, per-parameter norms of a step.
 // They run behind the backward pass inside the step's graph region; the host copies a record of a few dozen numbers.
+// lvsr_utterance_stats is the decode report's share (lvsr/main.py:732-736, 778-790, 816-823): cost, alignment spread and penalty per utterance.
 //
 // Determinism: no floating-point atomics.  Every kernel pair is "fixed slices -> partials, one work-group adds the partials": the
 // slices and the trees depend on the sizes alone, so eager launches, captured launches and graph replays give the same bits.
@@ -86,6 +87,83 @@ __global__ __launch_bounds__(OBS_THREADS) void obs_align_sum_kernel(const double
     }
     obs_block_sum<3>(s, red);
     if (threadIdx.x < 3) out[threadIdx.x] = (accumulate ? out[threadIdx.x] : 0.0) + red[threadIdx.x][0];
+}
+
+// ---- per-utterance alignment and cost (the decode report) ---------------------------------------------------------------------
+__device__ __forceinline__ double obs_shfl_xor_f64(double v, int o) {
+    int h[2];
+    memcpy(h, &v, sizeof(v));
+    h[0] = __shfl_xor(h[0], o, 64);
+    h[1] = __shfl_xor(h[1], o, 64);
+    memcpy(&v, h, sizeof(v));
+    return v;
+}
+__device__ __forceinline__ double obs_wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += obs_shfl_xor_f64(v, o);
+    return v;
+}
+
+// one wave per row (l,b), over the utterance's own attended length n = lengths[b] (NULL: T'): partials[3 row] = m cost,
+// [3 row + 1] = m sqrt(max(E2 - E1^2, 0)) with the moments in float64, [3 row + 2] = m sum_{t<n} max(C[l,b,t] - C[l-1,b,t], 0) with
+// the float32 scan of obs_align_rows_kernel (l = 0: 0).  A row whose mask is 0 writes zeros and reads neither weights nor costs.
+__global__ __launch_bounds__(OBS_THREADS) void obs_utt_rows_kernel(const float* w, long long ldw, int rows, int B, int Tp, const float* mask,
+                                                                   const float* costs, const int* lengths, double* partials) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    double* out = partials + 3 * (size_t)row;
+    const float m = mask ? mask[row] : 1.f;
+    if (m == 0.f) {                                        // (uniform over the wave)
+        if (lane < 3) out[lane] = 0.0;
+        return;
+    }
+    int n = lengths ? lengths[row % B] : Tp;
+    n = n < 0 ? 0 : n > Tp ? Tp : n;
+    const float* cur = w + (size_t)row * ldw;
+    const float* prev = row >= B ? cur - (size_t)B * ldw : nullptr;
+    float carry1 = 0.f, carry0 = 0.f, pen = 0.f;
+    double e1 = 0.0, e2 = 0.0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int t = c0 + lane;
+        const float a = t < n ? cur[t] : 0.f;
+        const double at = (double)a * (double)t;           // exact while t < 2^29
+        e1 += at;
+        e2 += at * (double)t;
+        if (prev) {                                        // (uniform over the wave)
+            const float p = t < n ? prev[t] : 0.f;
+            const float s1 = obs_wave_scan(a, lane) + carry1, s0 = obs_wave_scan(p, lane) + carry0;
+            if (t < n) pen += fmaxf(s1 - s0, 0.f);
+            carry1 = obs_last_lane(s1, lane);
+            carry0 = obs_last_lane(s0, lane);
+        }
+    }
+    pen = wave_sum(pen);
+    e1 = obs_wave_sum_f64(e1);
+    e2 = obs_wave_sum_f64(e2);
+    if (lane == 0) {
+        const double md = (double)m;
+        out[0] = costs ? md * (double)costs[row] : 0.0;
+        out[1] = md * sqrt(fmax(e2 - e1 * e1, 0.0));
+        out[2] = md * (double)pen;
+    }
+}
+
+// one wave per utterance b: out[b] = (sum_l partials[3 (l B + b) + k], k < 3; sum_l mask[l,b]), lanes strided over the labels, then
+// the xor tree, all in float64
+__global__ __launch_bounds__(64) void obs_utt_sum_kernel(const double* partials, const float* mask, int L, int B, double* out) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int l = lane; l < L; l += 64) {
+        const size_t row = (size_t)l * B + b;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s[k] += partials[3 * row + k];
+        s[3] += mask ? (double)mask[row] : 1.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) s[k] = obs_wave_sum_f64(s[k]);
+    if (lane == 0)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) out[4 * (size_t)b + k] = s[k];
 }
 
 // ---- min, max, sum |x| ----------------------------------------------------------------------------------------------------------
@@ -215,6 +293,19 @@ int lvsr_alignment_stats(void* stream, const float* weights, long long ldw, int 
     hipLaunchKernelGGL(obs_align_rows_kernel, dim3((rows + 3) / 4), dim3(OBS_THREADS), 0, s, weights, ldw, rows, B, Tp, mask, partials);
     hipLaunchKernelGGL(obs_align_sum_kernel, dim3(1), dim3(OBS_THREADS), 0, s, (const double*)partials, mask, rows, out, accumulate);
     return lvsr_check_launch("lvsr_alignment_stats");
+}
+
+int lvsr_utterance_stats(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask, const float* costs,
+                         const int* lengths, double* partials, double* out) {
+    LVSR_REQUIRE(weights && partials && out, "lvsr_utterance_stats: null argument");
+    LVSR_REQUIRE(L > 0 && B > 0 && Tp > 0 && ldw >= Tp, "lvsr_utterance_stats: bad sizes (L, B, T' > 0; ldw >= T')");
+    LVSR_REQUIRE((long long)L * B <= (1ll << 30), "lvsr_utterance_stats: more than 2^30 rows");
+    const int rows = L * B;
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(obs_utt_rows_kernel, dim3((rows + 3) / 4), dim3(OBS_THREADS), 0, s, weights, ldw, rows, B, Tp, mask, costs, lengths,
+                       partials);
+    hipLaunchKernelGGL(obs_utt_sum_kernel, dim3(B), dim3(64), 0, s, (const double*)partials, mask, L, B, out);
+    return lvsr_check_launch("lvsr_utterance_stats");
 }
 
 int lvsr_tensor_stats(void* stream, const float* x, long long n, int use_floor, float floor, double* partials, double* out) {

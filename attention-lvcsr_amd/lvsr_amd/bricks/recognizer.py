@@ -349,6 +349,101 @@ class SpeechRecognizer(object):
         torch.cuda.synchronize() if self.device.type == "cuda" else None
         return [cm[:, 0].cpu().numpy(), last["weights"][:, 0, :].cpu().numpy(), last["energies"][:, 0, :].cpu().numpy()]
 
+    def _pad_recordings(self, recordings, pad_to):
+        """list of (T_i, F) arrays -> x (T,B,F), mask (T,B) float32, T the longest length rounded up to a multiple of `pad_to`"""
+        recs = [numpy.asarray(r, dtype=numpy.float32).reshape(len(r), -1) for r in recordings]
+        T = max(len(r) for r in recs)
+        T = (T + pad_to - 1) // pad_to * pad_to
+        x = numpy.zeros((T, len(recs), recs[0].shape[1]), numpy.float32)
+        m = numpy.zeros((T, len(recs)), numpy.float32)
+        for i, r in enumerate(recs):
+            x[: len(r), i] = r
+            m[: len(r), i] = 1.0
+        return x, m
+
+    @staticmethod
+    def _pad_labels(seqs):
+        """list of label sequences -> labels (L,B) int64 (padded with 0), mask (L,B) float32"""
+        L = max(len(s) for s in seqs)
+        y = numpy.zeros((L, len(seqs)), numpy.int64)
+        m = numpy.zeros((L, len(seqs)), numpy.float32)
+        for i, s in enumerate(seqs):
+            y[: len(s), i] = s
+            m[: len(s), i] = 1.0
+        return y, m
+
+    def analyze_batch(self, recordings, groundtruths, predictions=None, want_alignments=False, pad_to=64):
+        """`analyze` for a chunk of utterances in one ragged pass, with the report's reductions on the device (lvsr/main.py:732-736,
+        778-790, 816-823).  `recordings`: list of (T_i, F) arrays; `groundtruths`: list of label sequences; `predictions`: None, or a
+        list of label sequences / None entries (an empty prediction counts as None: Theano's scan has no 0-length sequences,
+        main.py:816-817).  Under an mse criterion every ground truth ends in EOS, as in training.
+        -> one dict per utterance: groundtruth = dict(cost, weights_std, monotonicity_penalty, length), prediction = the same for the
+        prediction — its cost taken against the ground truth, as analyze(inputs, groundtruth, prediction) does — or None.
+        ONE encoder pass (padded as `compute_contexts_batch` pads) and one teacher-forced decoder pass per label set on the same
+        contexts, the second over the utterances that have a prediction only; behind each, lvsr_utterance_stats reduces cost matrix and
+        alignment to four numbers per utterance, which are all that is copied to the host — one synchronisation per call.
+        `want_alignments`: each entry also carries `weights` and `energies` (L_i, T'_i), cut to the utterance's own labels and
+        attended length (more copies)."""
+        from ..observables import utterance_stats
+        B = len(recordings)
+        if B == 0:
+            return []
+        if len(groundtruths) != B or (predictions is not None and len(predictions) != B):
+            raise ValueError("analyze_batch: %d recordings, %d groundtruths%s" % (
+                B, len(groundtruths), "" if predictions is None else ", %d predictions" % len(predictions)))
+        gts = [[int(t) for t in g] for g in groundtruths]
+        if any(len(g) == 0 for g in gts):
+            raise ValueError("analyze_batch: an empty groundtruth")
+        preds = [None] * B if predictions is None else [None if p is None or len(p) == 0 else [int(t) for t in p] for p in predictions]
+        cols = [i for i, p in enumerate(preds) if p is not None]
+        dev, gen, ws = self.device, self.generator, self.ws
+        x, xm = self._pad_recordings(recordings, pad_to)
+        y, ym = self._pad_labels(gts)
+        aligned = {}
+
+        def keep(which, index, Ls):
+            """the alignments of a pass, cut on the host"""
+            W, E = gen.last["weights"].cpu().numpy(), gen.last["energies"].cpu().numpy()
+            for j, i in enumerate(index):
+                aligned[which, i] = (W[: Ls[j], j, : tp_host[i]].copy(), E[: Ls[j], j, : tp_host[i]].copy())
+
+        with self._on_stream():
+            xb, xmb = self._t(x, torch.float32, "recordings"), self._t(xm, torch.float32, "recordings_mask")
+            yb, ymb = self._t(y, torch.int64, "labels"), self._t(ym, torch.float32, "labels_mask")
+            encoded, encoded_mask = self.encoder.apply(self.bottom.apply(xb, False), xmb, save_for_backward=False)
+            lengths = encoded_mask.sum(dim=0).to(torch.int32)
+            tp_host = lengths.cpu().numpy().tolist() if want_alignments else None
+            record = ws.get("analyze.record", (2, B, 4), torch.float64)
+            cm = gen.cost_matrix(yb, ymb, attended=encoded, attended_mask=encoded_mask, save_for_backward=False)
+            utterance_stats(self.lib, gen.last["weights"], ymb, cm, record[0], ws, lengths=lengths)
+            if want_alignments:
+                keep("groundtruth", range(B), [len(g) for g in gts])
+            if cols:
+                p, pm = self._pad_labels([preds[i] for i in cols])
+                pb, pmb = self._t(p, torch.int64, "prediction"), self._t(pm, torch.float32, "prediction_mask")
+                if len(cols) == B:
+                    enc, encm, gtb, lens = encoded, encoded_mask, yb, lengths
+                else:
+                    # the columns that have a prediction, gathered: no all-masked column reaches the decoder kernels
+                    idx = torch.tensor(cols, dtype=torch.int64).to(dev, non_blocking=True)
+                    enc, encm = encoded.index_select(1, idx), encoded_mask.index_select(1, idx)
+                    gtb, lens = yb.index_select(1, idx), lengths.index_select(0, idx)
+                cm = gen.cost_matrix(pb, pmb, attended=enc, attended_mask=encm, save_for_backward=False, groundtruth=gtb)
+                utterance_stats(self.lib, gen.last["weights"], pmb, cm, record[1, :len(cols)], ws, lengths=lens)
+                if want_alignments:
+                    keep("prediction", cols, [len(preds[i]) for i in cols])
+            host = record.cpu().numpy()                       # the one synchronisation
+
+        def entry(r):
+            n = int(r[3])
+            return dict(cost=float(r[0]), weights_std=float(r[1]) / n, monotonicity_penalty=float(r[2]), length=n)
+        out = [dict(groundtruth=entry(host[0, i]), prediction=None) for i in range(B)]
+        for j, i in enumerate(cols):
+            out[i]["prediction"] = entry(host[1, j])
+        for (which, i), (W, E) in aligned.items():
+            out[i][which].update(weights=W, energies=E)
+        return out
+
     # ---- decoding (recognizer.py:496-533) ------------------------------------------------------------
     def compute_contexts(self, recordings):
         """Encoder at batch 1 with NO input mask (init_beam_search builds the graph with use_mask=False,
@@ -365,14 +460,7 @@ class SpeechRecognizer(object):
         to a common length (a multiple of `pad_to` frames, so that few distinct shapes — and captured graphs — occur) under an input
         mask.  A masked recurrent step keeps its state (recurrent.py:297-300), so every utterance's contexts are those of its own
         unmasked batch-1 pass (`compute_contexts`) up to its own attended length."""
-        recs = [numpy.asarray(r, dtype=numpy.float32).reshape(len(r), -1) for r in recordings]
-        T = max(len(r) for r in recs)
-        T = (T + pad_to - 1) // pad_to * pad_to
-        x = numpy.zeros((T, len(recs), recs[0].shape[1]), numpy.float32)
-        m = numpy.zeros((T, len(recs)), numpy.float32)
-        for i, r in enumerate(recs):
-            x[: len(r), i] = r
-            m[: len(r), i] = 1.0
+        x, m = self._pad_recordings(recordings, pad_to)
         xb, mb = self._t(x, torch.float32, "recordings"), self._t(m, torch.float32, "recordings_mask")
         encoded, encoded_mask = self.encoder.apply(self.bottom.apply(xb, False), mb, save_for_backward=False)
         self.generator.init_generation(encoded, encoded_mask)

@@ -29,52 +29,110 @@ def _searched(recognizer, utterances, batch, kw):
             yield item + (res,)
 
 
+def _score_each(recognizer, recordings, groundtruth, recognized):
+    """The two `analyze` calls of one utterance -> (groundtruth scores, scores of the hypothesis or None)."""
+    inputs = {"recordings": recordings}
+    gt_cost, gt_weights, _ = recognizer.analyze(inputs, numpy.asarray(groundtruth))
+    gt = dict(cost=float(gt_cost.sum()), weights_std=float(weights_std(gt_weights[:, None, :])),
+              monotonicity_penalty=float(monotonicity_penalty(gt_weights[:, None, :])))
+    if not recognized:
+        return gt, None
+    rec_cost, _, _ = recognizer.analyze(inputs, numpy.asarray(groundtruth), numpy.asarray(recognized))
+    return gt, dict(cost=float(rec_cost.sum()))
+
+
+def _best(result):
+    """the best hypothesis of a search result ([] where no candidate was found; None: no search was run)"""
+    if result is None or isinstance(result, CandidateNotFoundError):
+        return []
+    if isinstance(result, Exception):
+        raise result
+    return result[0][0]
+
+
+def _scored(recognizer, utterances, batch, kw, score_batch, nll_only):
+    """(number, groundtruth, search result / exception / None under `nll_only`, groundtruth scores, hypothesis scores or None), in
+    order.  `score_batch` = 0: utterance by utterance through `analyze`; N > 0: chunks of N utterances, each searched and then scored
+    by ONE `analyze_batch` call."""
+    if score_batch <= 0:
+        items = ((n, x, g, None) for n, (x, g) in enumerate(utterances)) if nll_only else _searched(recognizer, utterances, batch, kw)
+        for number, recordings, groundtruth, result in items:
+            groundtruth = [int(t) for t in groundtruth]
+            yield (number, groundtruth, result) + _score_each(recognizer, recordings, groundtruth, _best(result))
+        return
+    chunk = []
+
+    def flush():
+        results = [None] * len(chunk) if nll_only else [r for _, _, _, r in _searched(recognizer, [c[1:] for c in chunk], batch, kw)]
+        scores = recognizer.analyze_batch([c[1] for c in chunk], [c[2] for c in chunk],
+                                          None if nll_only else [_best(r) for r in results])
+        for (number, _, groundtruth), result, sc in zip(chunk, results, scores):
+            yield number, groundtruth, result, sc["groundtruth"], sc["prediction"]
+
+    for number, (recordings, groundtruth) in enumerate(utterances):
+        chunk.append((number, recordings, [int(t) for t in groundtruth]))
+        if len(chunk) == score_batch:
+            for item in flush():
+                yield item
+            chunk = []
+    if chunk:
+        for item in flush():
+            yield item
+
+
 def search(recognizer, utterances, beam_size=10, char_discount=0.0, round_to_inf=1e9, stop_on="patience", to_words=None,
-           report=None, batch=1):
+           report=None, batch=1, score_batch=0, nll_only=False):
     """-> dict(per_utterance=[...], cer=, wer=, nll_groundtruth=, nll_recognized=).  `to_words(labels) -> list[str]` turns a
     label sequence into words for WER (the reference decodes characters with its character map, lvsr/main.py:788-800).
     `batch` (an addition): utterances decoded side by side, several times the throughput on a GPU.  An utterance's hypotheses do not
     depend on the batch it is decoded in for any batch > 1 (trailing chunks and one-utterance chunks included: the readout's merge
     products always run through lvsr_readout_merge there); against batch = 1 (per-row VALU products below 64 rows: another float32
     summation order) costs agree to ~1e-5 relative and candidates closer than that may swap ranks.  A host-side language model
-    or a validator decode one utterance at a time whatever `batch` says (BeamSearch.search_batch)."""
-    recognizer.init_beam_search(beam_size)
+    or a validator decode one utterance at a time whatever `batch` says (BeamSearch.search_batch).
+    `score_batch` (an addition): 0 = every utterance is scored by two `analyze` calls at batch 1, its alignment reduced on the host;
+    N > 0 = utterances are taken in chunks of N, a chunk is searched (side by side with `batch` > 1) and then scored by one
+    `SpeechRecognizer.analyze_batch` call: one encoder pass, two ragged decoder passes, the report's reductions on the device.  The
+    rows carry the same keys either way and `report(row)` is called in utterance order.
+    `nll_only` (the reference's --nll-only, lvsr/main.py:793-795): no search; the rows hold the ground-truth scores only and the
+    result has no cer / wer / nll_recognized.
+    nll_groundtruth: the mean ground-truth cost per utterance (the reference's "Average groundtruth cost"); nll_recognized: the mean
+    cost of the best hypothesis over the utterances that have one (nan when none has)."""
+    if not nll_only:
+        recognizer.init_beam_search(beam_size)
     rows, tot_err, tot_len, tot_werr, tot_wlen = [], 0, 0, 0, 0
+    tot_gt, tot_rec, num_rec = 0.0, 0.0, 0
     kw = dict(char_discount=char_discount, round_to_inf=round_to_inf, stop_on=stop_on)
-    for number, recordings, groundtruth, result in _searched(recognizer, utterances, int(batch), kw):
-        groundtruth = [int(t) for t in groundtruth]
-        inputs = {"recordings": recordings}
+    for number, groundtruth, result, gt, rec in _scored(recognizer, utterances, int(batch), kw, int(score_batch), bool(nll_only)):
         row = dict(number=number, groundtruth=groundtruth)
+        recognized = _best(result)
         if isinstance(result, CandidateNotFoundError):                       # lvsr/main.py:808-813
-            recognized = []
             row.update(recognized=[], search_cost=float("nan"), error="CandidateNotFoundError")
-        elif isinstance(result, Exception):
-            raise result
-        else:
-            outputs, search_costs = result
-            recognized = outputs[0]
-            row.update(recognized=recognized, search_cost=search_costs[0])
-        gt_cost, gt_weights, _ = recognizer.analyze(inputs, numpy.asarray(groundtruth))
-        row.update(groundtruth_cost=float(gt_cost.sum()),
-                   weights_std=float(weights_std(gt_weights[:, None, :])),
-                   monotonicity_penalty=float(monotonicity_penalty(gt_weights[:, None, :])))
-        if recognized:
-            rec_cost, _, _ = recognizer.analyze(inputs, numpy.asarray(groundtruth), numpy.asarray(recognized))
-            row["recognized_cost"] = float(rec_cost.sum())
-        err = int(edit_distance(groundtruth, recognized))
-        row.update(char_errors=err, cer=err / float(len(groundtruth)))
-        tot_err += err
-        tot_len += len(groundtruth)
-        if to_words is not None:
-            gw, rw = to_words(groundtruth), to_words(recognized)
-            werr = int(edit_distance(gw, rw))
-            row.update(word_errors=werr, wer=werr / float(max(1, len(gw))))
-            tot_werr += werr
-            tot_wlen += len(gw)
+        elif result is not None:
+            row.update(recognized=recognized, search_cost=result[1][0])
+        row.update(groundtruth_cost=gt["cost"], weights_std=gt["weights_std"], monotonicity_penalty=gt["monotonicity_penalty"])
+        tot_gt += gt["cost"]
+        if rec is not None:
+            row["recognized_cost"] = rec["cost"]
+            tot_rec += rec["cost"]
+            num_rec += 1
+        if not nll_only:
+            err = int(edit_distance(groundtruth, recognized))
+            row.update(char_errors=err, cer=err / float(len(groundtruth)))
+            tot_err += err
+            tot_len += len(groundtruth)
+            if to_words is not None:
+                gw, rw = to_words(groundtruth), to_words(recognized)
+                werr = int(edit_distance(gw, rw))
+                row.update(word_errors=werr, wer=werr / float(max(1, len(gw))))
+                tot_werr += werr
+                tot_wlen += len(gw)
         rows.append(row)
         if report is not None:
             report(row)
-    out = dict(per_utterance=rows, cer=tot_err / float(max(1, tot_len)))
+    out = dict(per_utterance=rows, nll_groundtruth=tot_gt / float(max(1, len(rows))))
+    if nll_only:
+        return out
+    out.update(cer=tot_err / float(max(1, tot_len)), nll_recognized=tot_rec / num_rec if num_rec else float("nan"))
     if to_words is not None:
         out["wer"] = tot_werr / float(max(1, tot_wlen))
     return out

@@ -67,6 +67,21 @@ def alignment_stats(lib, weights, mask, out, ws, accumulate=False):
              ptr(out), int(bool(accumulate)))
 
 
+def utterance_stats(lib, weights, mask, costs, out, ws, lengths=None):
+    """Enqueue lvsr_utterance_stats on weights (L,B,T') — rows may be strided views of a larger buffer —, mask / costs (L,B) or
+    None, lengths (B) int32 or None (each utterance's own attended length), into `out` (B,4) float64: per utterance the summed
+    cost, weights_std times its label count, monotonicity_penalty and the label count."""
+    L, B, Tp = (int(s) for s in weights.shape)
+    assert weights.stride(2) == 1 and weights.stride(0) == B * weights.stride(1), "the (l,b) rows must be equally spaced"
+    for t in (mask, costs):
+        assert t is None or (t.is_contiguous() and tuple(t.shape) == (L, B) and t.dtype == torch.float32)
+    assert lengths is None or (lengths.is_contiguous() and tuple(lengths.shape) == (B,) and lengths.dtype == torch.int32)
+    assert out.is_contiguous() and tuple(out.shape) == (B, 4) and out.dtype == torch.float64
+    partials = ws.get("obs.utterance_partials", (3 * L * B,), torch.float64)
+    lib.call("lvsr_utterance_stats", lib.stream_for(out), ptr(weights), int(weights.stride(1)), L, B, Tp, ptr(mask), ptr(costs),
+             ptr(lengths), ptr(partials), ptr(out))
+
+
 def tensor_stats(lib, x, out, ws, floor=None):
     """Enqueue lvsr_tensor_stats on the contiguous tensor x into the three doubles of `out` (min, max, sum |x|)."""
     assert x.is_contiguous() and x.dtype == torch.float32

@@ -469,6 +469,20 @@ int lvsr_philox_normal(void* stream, long long seed, long long counter, long lon
  * accumulate != 0: out[k] += (validation: one record over all batches), else out[k] =. */
 int lvsr_alignment_stats(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask,
                          double* partials, double* out, int accumulate);
+/* The decode report per utterance (weight_statistics and the summed costs of lvsr/main.py:732-736, 778-790, 816-823) for a ragged
+ * batch: weights, ldw, mask as above, costs (L,B) or NULL, lengths (B) ints or NULL = each utterance's own attended length n_b
+ * (clamped to [0, T']; NULL: T'): what lies behind it is padding and is not read.  out (B,4) float64, with m = mask:
+ *   out[b][0] = sum_l m[l,b] costs[l,b]                                    (costs NULL: 0)
+ *   out[b][1] = sum_l m[l,b] sqrt(max(E2 - E1^2, 0)),  E1 = sum_{t<n_b} w[l,b,t] t,  E2 = sum_{t<n_b} w[l,b,t] t^2
+ *               (weights_std in front of its division by the number of labels)
+ *   out[b][2] = sum_{l>=1} m[l,b] sum_{t<n_b} max(C[l,b,t] - C[l-1,b,t], 0)   (monotonicity_penalty; L = 1: 0)
+ *   out[b][3] = sum_l m[l,b]
+ * One wave per row (l,b): the penalty is the float32 scan of lvsr_alignment_stats; the moments are float64 per lane (E2 - E1^2
+ * cancels five digits at T' = 200) folded by the xor tree.  A row whose mask is 0 writes zeros and reads nothing.  partials (3 L B
+ * doubles, scratch) are then added per utterance by one wave, lanes strided over the labels, in float64.  No atomics: every order
+ * depends on the sizes alone, so two runs give the same bits. */
+int lvsr_utterance_stats(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask,
+                         const float* costs, const int* lengths, double* partials, double* out);
 /* out[0] = min, out[1] = max (both exact; float32 values held in doubles), out[2] = sum |x| over the n contiguous floats of x;
  * use_floor != 0: over max(x, floor) instead (the gain matrix as RewardRegressionEmitter.cost sees it, lvsr/bricks/__init__.py:154).
  * Two stages: ceil(n / 8192) work-groups (at most 1024: the grid depends on n only) with float64 sums per thread and a fixed
