@@ -423,6 +423,9 @@ __global__ __launch_bounds__(256) void softmax_emit_kernel(const float* logits, 
     }
 }
 
+// gather / scatter put a row count into gridDim.y, which HIP limits to 65535
+#define GRID_Y_MAX 65535
+
 extern "C" {
 
 int lvsr_softmax_emit(void* stream, const float* logits, int ld, const float* uniforms, int n, int V, long long* outputs,
@@ -466,6 +469,8 @@ int lvsr_readout_merge(void* stream, const float* S, int lds, const float* WA, i
 int lvsr_gather_rows(void* stream, const float* table, int ldt, const long long* idx, int n, int nrows, int width,
                      const float* bias, float* out, int ldo) {
     if (n <= 0 || width <= 0) return LVSR_OK;
+    LVSR_REQUIRE(n <= GRID_Y_MAX, "lvsr_gather_rows: n = %d rows exceed the %d of one launch (one work-group row per output row)", n,
+                 GRID_Y_MAX);
     hipLaunchKernelGGL(gather_rows_kernel, dim3((width + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, table, ldt, idx, n,
                        nrows, width, bias, out, ldo);
     return lvsr_check_launch("lvsr_gather_rows");
@@ -474,6 +479,9 @@ int lvsr_gather_rows(void* stream, const float* table, int ldt, const long long*
 int lvsr_scatter_add_rows(void* stream, const float* src, int lds, const long long* idx, int n, int nrows, int width,
                           float* dst, int ldd, float beta) {
     if (nrows <= 0 || width <= 0) return LVSR_OK;
+    LVSR_REQUIRE(nrows <= GRID_Y_MAX,
+                 "lvsr_scatter_add_rows: nrows = %d rows exceed the %d of one launch (one work-group row per destination row)", nrows,
+                 GRID_Y_MAX);
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3((width + 255) / 256, nrows), dim3(256), 0, (hipStream_t)stream, src, lds,
                        idx, n, width, dst, ldd, beta);
     return lvsr_check_launch("lvsr_scatter_add_rows");

@@ -340,10 +340,12 @@ int lvsr_attdec_filter_grad(void* stream, const lvsr_attdec_args* f, const float
  * LookupTable.apply (libs/blocks/blocks/bricks/lookup.py:48-68) / OneOfNFeedback (lvsr/bricks/__init__.py:
  * 97-104); Maxout/Rectifier/Tanh (libs/blocks/blocks/bricks/simple.py:161-207); Softmax.log_probabilities,
  * categorical_cross_entropy (:315-371); SoftmaxEmitter.cost/costs (sequence_generators.py:780-791). */
-/* out[r,:] = table[idx[r],:] + bias  (rows with idx outside [0,nrows) read as zero) */
+/* out[r,:] = table[idx[r],:] + bias  (rows with idx outside [0,nrows) read as zero).  Limit: n <= 65535 (one work-group row of the
+ * grid per output row); more is refused */
 int lvsr_gather_rows(void* stream, const float* table, int ldt, const long long* idx, int n, int nrows, int width,
                      const float* bias, float* out, int ldo);
-/* dst[v,:] = beta*dst[v,:] + sum_{r: idx[r]==v} src[r,:]  (deterministic) */
+/* dst[v,:] = beta*dst[v,:] + sum_{r: idx[r]==v} src[r,:]  (deterministic: ascending r; idx outside [0,nrows) is ignored; beta = 0:
+ * dst is not read).  Limit: nrows <= 65535 (one work-group row of the grid per destination row); more is refused.  n is not limited */
 int lvsr_scatter_add_rows(void* stream, const float* src, int lds, const long long* idx, int n, int nrows, int width,
                           float* dst, int ldd, float beta);
 /* kind: 0 identity, 1 Maxout(2), 2 Rectifier, 3 Tanh; x (n,P) -> y (n,P or P/2) */
