@@ -253,3 +253,12 @@ class Data(object):
             b = emit(buf)
             if b is not None:
                 yield b
+
+
+def __getattr__(name):
+    # DeviceData (the dataset resident in device memory, lvsr_amd/device_data.py) is part of this module's surface; it is imported
+    # on first use because it needs the native library's binding, which plain host pipelines do not
+    if name == "DeviceData":
+        from .device_data import DeviceData
+        return DeviceData
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -98,10 +98,18 @@ def _average_row(window, iterations, epoch):
     return row
 
 
+def _on_device(data, device, lib):
+    """`data` resident on `device` (a DeviceData is passed through)."""
+    from .device_data import DeviceData
+    return data if isinstance(data, DeviceData) else DeviceData(data, device=device, lib=lib)
+
+
 def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=None, distributed=None, search_subset=10,
-          resume=False, stage=None, observables=None):
+          resume=False, stage=None, observables=None, device_data=False):
     """One stage.  `config`: a (stage) configuration mapping with `net`, `training`, optional `regularization`,
-    `monitoring`, `initialization`; `data`: lvsr_amd.data.Data.  Returns (recognizer, log).
+    `monitoring`, `initialization`; `data`: lvsr_amd.data.Data or lvsr_amd.data.DeviceData.  Returns (recognizer, log).
+    `device_data=True`: `data` is uploaded to the training device once (DeviceData) and every minibatch is assembled there by one
+    launch instead of by host Python per utterance; same batches, bit for bit.
     `resume=True`: `params` is a checkpoint of THIS stage written by an earlier call: besides the parameters, the optimiser
     accumulators, the adaptive-clipping statistics and the epoch / iteration / best-cost counters are restored from its
     `_training_state` member, so the recipe continues where it stopped (the reference resumes from its pickled main loop).
@@ -131,6 +139,8 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
     if params:
         rec.load_params(params)
     rank, world, barrier = _dist_state(distributed)
+    if device_data:
+        data = _on_device(data, rec.device, rec.lib)
     # adaptive noise divides its model cost by the size of the training set (lvsr/main.py:434)
     if observables is None:
         observables = mon.get("observables")
@@ -254,10 +264,12 @@ def train(config, data, save_path, params=None, device="cuda:0", lib=None, log=N
     return rec, log
 
 
-def train_multistage(config, data, save_path, params=None, start_stage=None, resume=False, **kwargs):
+def train_multistage(config, data, save_path, params=None, start_stage=None, resume=False, device_data=False, **kwargs):
     """lvsr/main.py:896-922: stages in `number` order; stage k > 0 restarts from `<save_path>/<stage k-1><restart_from>.zip`.
     `resume=True` applies to the FIRST stage run only (its `params` is that stage's own checkpoint); later stages start fresh
-    from their predecessor's parameters."""
+    from their predecessor's parameters.  `device_data=True`: as in `train`; the dataset is uploaded once for all stages."""
+    if device_data:
+        data = _on_device(data, kwargs.get("device", "cuda:0"), kwargs.get("lib"))
     if not getattr(config, "multi_stage", False):
         return train(config, data, save_path, params, resume=resume, **kwargs)
     rank, _, barrier = _dist_state(kwargs.get("distributed"))

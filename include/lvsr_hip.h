@@ -694,6 +694,32 @@ int lvsr_fbank_batch(void* stream, const short* wav, const long long* wav_off, c
 int lvsr_add_deltas_cmvn_batch(void* stream, const float* feats, const int* frame_off, int n, int total_frames, int dim, const float* mean,
                                const float* istd, float* out);
 
+/* ---- minibatch assembly from a device-resident training set -------------------------------------------
+ * fuel Padding (libs/fuel/fuel/transformers/__init__.py:691-720) + the switch of the first two axes + ForceCContiguous of the
+ * reference's stream (lvsr/datasets/__init__.py:303-309), which the reference runs in host Python for every minibatch.  The
+ * training set is static, so it is normalised and uploaded once as a ragged store: utterance u owns frames
+ * [frame_off[u], frame_off[u+1]) of `frames` and labels [label_off[u], label_off[u+1]) of `labels` (all offsets 64-bit: a
+ * 14 GB store has 3.6 G floats).  ONE launch writes EVERY element of the four outputs, padding included (zeros; masks exactly
+ * 0.0 / 1.0; labels 0 where masked): no memset in front, the outputs may hold anything on entry.  Column b of the outputs is
+ * utterance index[b]; `index` may point into a longer device table (the epoch's order).  The kernel stays inside its buffers
+ * whatever the arguments: an utterance longer than T (L) is cut there, an index outside [0, n) gives an empty column — the Python
+ * layer (lvsr_amd/device_data.py) refuses both before launching.  Values are copied, never computed: the outputs are those of
+ * Data.pad_batch bit for bit.  No LDS, no atomics (csrc/batch.hip). */
+typedef struct lvsr_batch_args {
+    const float* frames;          /* (total_frames, F): all utterances' frames back to back, already normalised */
+    const long long* frame_off;   /* (n + 1): first frame of utterance u; frame_off[n] = total_frames */
+    const long long* labels;      /* all utterances' labels back to back, BOS / EOS already in place */
+    const long long* label_off;   /* (n + 1) */
+    const long long* index;       /* (B) device: utterances of this minibatch in column order */
+    long long n;                  /* utterances in the store */
+    int B, T, L, F;
+    float* recordings;            /* (T,B,F) out */
+    float* recordings_mask;       /* (T,B)   out */
+    long long* out_labels;        /* (L,B)   out */
+    float* labels_mask;           /* (L,B)   out */
+} lvsr_batch_args;
+int lvsr_assemble_batch(void* stream, const lvsr_batch_args* a);
+
 #ifdef __cplusplus
 }
 #endif
