@@ -11,18 +11,17 @@ the decoder and `groundtruth=` what its rewards are measured against.  All arith
 is in the C-ABI library; torch only owns buffers/views.
 """
 import ctypes
-import os
 
 import numpy
 import torch
 
 from ..native import ptr
+from .beam_state import BeamState
 
 ACT_KIND = {"identity": 0, "maxout2": 1, "rectifier": 2, "tanh": 3}
 NORMALIZER_KIND = {"softmax": 0, "logistic": 1, "relu": 2}
 PRIOR_KIND = {"expanding": 0, "window_around_mean": 1, "window_around_median": 2}
 ATT_MS = 32     # match-dim slice per work-group in the energy kernels (csrc/decoder.h)
-CTL = dict(nlive=0, pos=1, done=2, nfin=3, patience=4, nsel=5, err=6, steps=7)      # words of a beam search's control block (csrc/beam.hip)
 
 
 def _f32(x):
@@ -31,6 +30,7 @@ def _f32(x):
 
 class SequenceGenerator(object):
     language_model = None
+    current_search = None        # the BeamState of the search set begun last (`beam_begin`)
 
     def __init__(self, dims, store, lib, workspace, use_graph=True, use_persistent=None):
         self.d = dims
@@ -461,7 +461,7 @@ class SequenceGenerator(object):
         dev = labels.device
         out = self.ws.get("gen.lm_add", (L, B, self.d.V))
         st = lm.initial_states(B)
-        on_dev = getattr(lm, "on_device", False)
+        on_dev = lm.on_device
         lab = labels if on_dev else labels.cpu().numpy()
         msk = None if ym is None else (ym if on_dev else ym.cpu().numpy())
         for i in range(L):
@@ -734,145 +734,13 @@ class SequenceGenerator(object):
             lib.call("lvsr_attdec_fwd", st, ctypes.byref(lib.make("lvsr_attdec_args", **fg)), 0)
         return dict(states=S[1:], outputs=outputs, weighted_averages=full["WA"], weights=W[1:], energies=full["EN"], costs=costs)
 
-    # ---- device-resident beam search (csrc/beam.hip): state of one search + the launches of one position ------------------
     def beam_begin(self, K, eol, max_length, ignore_first_eol=False, char_discount=0.0, round_to_inf=1e9, stop_on="patience",
                    force_merge=False):
-        """Allocate (once per (K, T', max_length)) and reset the device state of a beam search over the contexts set by
-        `init_generation`: hypothesis 0 = initial state / initial glimpses (search.py:287-299), every other row a copy.
-        After `init_generation` on a batch of N utterances: N searches side by side (`max_length` = one limit per utterance),
-        search g in rows [g K, g K + K) of every state buffer and block g of the bookkeeping buffers (lvsr_beam_args.groups)."""
-        d, p, n_, lib, ws, g = self.d, self.store.p, self.n, self.lib, self.ws, self._gen
+        """Begin the device-resident beam search(es) over the contexts set by `init_generation` -> its `BeamState`
+        (bricks/beam_state.py), from now on the one search set this generator serves: the launches of an earlier state raise."""
         self._check_emitter()
-        Tp, dev = g["Tp"], g["A"].device
-        lm = self.language_model
-        on_dev_lm = lm is not None and getattr(lm, "on_device", False)
-        G = int(g.get("N", 1))
-        if G > 1:
-            limits = [int(m) for m in max_length]
-            assert len(limits) == G
-            assert lm is None or on_dev_lm, "batched search: language model on the device"
-            # capacity of the history buffers (and part of the step graph's key): the largest limit, rounded up so that batches of
-            # slightly different lengths share buffers and graph; every search stops at its own limit (ctl word 8)
-            max_length = (max(limits) + 31) // 32 * 32
-            return self._beam_begin(K * G, K, G, limits, eol, max_length, ignore_first_eol, char_discount, round_to_inf, stop_on, True)
-        return self._beam_begin(K, K, 1, None, eol, max_length, ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge)
-
-    def _beam_begin(self, R, K, G, limits, eol, max_length, ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge=False):
-        """R = G * K rows: G searches of beam K.  `force_merge`: the readout's merge products through lvsr_readout_merge whatever
-        the number of rows (every batched decode, so that an utterance's hypotheses do not depend on how many others share its
-        launches: a row of that kernel is summed in the same order in any batch)."""
-        d, p, n_, lib, ws, g = self.d, self.store.p, self.n, self.lib, self.ws, self._gen
-        Tp, dev = g["Tp"], g["A"].device
-        lm = self.language_model
-        on_dev_lm = lm is not None and getattr(lm, "on_device", False)
-        tag = ".K%d" % K if G == 1 else ".K%dx%d" % (K, G)
-        K_one, K = K, R            # below, K counts ROWS of the state buffers; K_one is the beam size
-        i32, i64, f64 = torch.int32, torch.int64, torch.float64
-        fin_cap = 2 * K_one if stop_on == "patience" else K_one * (max_length + 1)
-        pos_needed = self._pos_needed()
-        SW = self._state_width()
-        stacked = d.n_dec > 1          # bricks/generator_stack.py: pass B is the attention block and one GRU block per layer
-
-        def attbufs(which, fork):
-            t = tag + which
-            return self._attdec_bufs("bs.", t, 1, K, Tp, xg=ws.get("bs.xg" + t, (K, 3 * d.D)) if fork else None, ymask=None)
-        A_, B_ = attbufs("a", False), attbufs("b", True)
-        gshape = (lambda *dims: dims) if G == 1 else (lambda *dims: (G,) + dims)
-        st = dict(K=K_one, rows=K, groups=G, Tp=Tp, max_length=int(max_length), limits=limits, fin_cap=fin_cap, A=A_, B=B_,
-                  ctl=ws.get("bs.ctl" + tag, gshape(16), i32), fctl=ws.get("bs.fctl" + tag, gshape(4)),
-                  neglogp=ws.get("bs.neglogp" + tag, (K, d.V)), running=ws.get("bs.running" + tag, (K,)),
-                  live_col=ws.get("bs.live_col" + tag, (K,), i32),
-                  hist_parent=ws.get("bs.hist_parent" + tag, gshape(max_length, K_one), i32),
-                  hist_char=ws.get("bs.hist_char" + tag, gshape(max_length, K_one), i32),
-                  hist_cost=ws.get("bs.hist_cost" + tag, gshape(max_length, K_one)),
-                  fin_pos=ws.get("bs.fin_pos" + tag, gshape(fin_cap), i32), fin_col=ws.get("bs.fin_col" + tag, gshape(fin_cap), i32),
-                  fin_cost=ws.get("bs.fin_cost" + tag, gshape(fin_cap)), fin_score=ws.get("bs.fin_score" + tag, gshape(fin_cap)),
-                  keep=ws.get("bs.keep" + tag, (K,), i32), chars=ws.get("bs.chars" + tag, (K,), i64),
-                  parents=ws.get("bs.parents" + tag, (K,), i32),
-                  fb=ws.get("bs.fb" + tag, (K, d.FB)) if d.embed else None, lm=None)
-        if lm is not None:
-            st["lm"] = dict(add_live=ws.get("bs.lm_add_live" + tag, (K, d.V)))
-            if on_dev_lm:
-                st["lm"].update(states_live=ws.get("bs.lm_sl" + tag, (K, 7), i64), weights_live=ws.get("bs.lm_wl" + tag, (K, 7), f64),
-                                states_sel=ws.get("bs.lm_ss" + tag, (K, 7), i64), weights_sel=ws.get("bs.lm_ws" + tag, (K, 7), f64),
-                                states_new=ws.get("bs.lm_sn" + tag, (K, 7), i64), weights_new=ws.get("bs.lm_wn" + tag, (K, 7), f64),
-                                add_new=ws.get("bs.lm_add_new" + tag, (K, d.V)))
-        pk = self._packed()
-        # window centres travel with the rows (select / compact move them), so neither pass recomputes slot 0: phases bit 2
-        skip_pos = 4 if pos_needed else 0
-        grp = dict(groups=G, group_Tp=g["lengths"]) if G > 1 else {}
-        fa = self._attdec_fields(pk, g["A"], g["PA"], g["Am"], 1, K, A_, phases=1 | skip_pos, step0=0, broadcast=True, **grp)
-        pos_word = st["ctl"].view(-1)[CTL["pos"]:]
-        st["argsA"] = lib.make("lvsr_attdec_args", step_dev=pos_word, **fa)
-        if stacked:
-            st["stepB"] = self._beam_step_blocks(pk, g, K, B_, skip_pos, pos_word, tag, **grp)
-        else:
-            fb_ = self._attdec_fields(pk, g["A"], g["PA"], g["Am"], 1, K, B_, phases=3 | skip_pos, step0=-1, broadcast=True, **grp)
-            # the select launch raises word 9 of a search's control block when pass B's glimpses would repeat pass A's row by row
-            # (and copies them): lvsr_beam_args.WA_live
-            st["argsB"] = lib.make("lvsr_attdec_args", step_dev=pos_word, skip=st["ctl"].view(-1)[9:], skip_stride=16, **fb_)     # runs after the select kernel moved on: step0 = -1
-        L = st["lm"] or {}
-        host_fork = d.embed or stacked      # the fork of the chosen characters as separate launches of pass B
-        st["args"] = lib.make(
-            "lvsr_beam_args", K=K_one, groups=G, V=d.V, eol=int(eol), ignore_first_eol=int(bool(ignore_first_eol)),
-            stop_on={"patience": 0, "optimistic_future_cost": 1}[stop_on], max_length=int(max_length), fin_cap=fin_cap, D=SW, Tp=Tp,
-            round_to_inf=float(numpy.float32(min(float(round_to_inf), 3.0e38))), char_discount=float(char_discount),
-            ctl=st["ctl"], fctl=st["fctl"], neglogp=st["neglogp"], running=st["running"], live_col=st["live_col"],
-            hist_parent=st["hist_parent"], hist_char=st["hist_char"], hist_cost=st["hist_cost"], fin_pos=st["fin_pos"],
-            fin_col=st["fin_col"], fin_cost=st["fin_cost"], fin_score=st["fin_score"], keep=st["keep"], chars=st["chars"],
-            parents=st["parents"], S_live=A_["S"][0], W_live=A_["W"][0], S_sel=B_["S"][0], W_sel=B_["W"][0],
-            lm_states_live=L.get("states_live"), lm_weights_live=L.get("weights_live"), lm_states_sel=L.get("states_sel"),
-            lm_weights_sel=L.get("weights_sel"), S_new=B_["S"][1], W_new=B_["W"][1], S_live_out=A_["S"][0], W_live_out=A_["W"][0],
-            lm_states_new=L.get("states_new"), lm_weights_new=L.get("weights_new"), lm_add_new=L.get("add_new"),
-            lm_states_live_out=L.get("states_live"), lm_weights_live_out=L.get("weights_live"),
-            lm_add_live_out=L.get("add_live") if on_dev_lm else None,
-            pos_live=A_["pos"][0] if pos_needed else None, pos_sel=B_["pos"][0] if pos_needed else None,
-            pos_new=B_["pos"][1] if pos_needed else None, pos_live_out=A_["pos"][0] if pos_needed else None,
-            # one-hot feedback: the fork of the chosen characters is a row gather the select launch does itself
-            fork_xg=None if host_fork else B_["xg"], fork_Wi=None if host_fork else p[n_["Wfi"]],
-            fork_Wg=None if host_fork else p[n_["Wfg"]], fork_bi=None if host_fork else p[n_["bfi"]],
-            fork_bg=None if host_fork else p[n_["bfg"]], fork_rows=0 if host_fork else d.FB,
-            **({} if stacked else dict(WA_live=A_["WA"][0], WA_sel=B_["WA"][0], W1_live=A_["W"][1], W1_sel=B_["W"][1], E=d.E,
-                                       pos1_live=A_["pos"][1] if pos_needed else None, pos1_sel=B_["pos"][1] if pos_needed else None)))
-        # many rows (batched search): the merge products as 16-row tiles in a launch of their own (lvsr_readout_merge)
-        R1 = ws.get("bs.R1" + tag, (K, d.P)) if (K >= self.MERGE_ROWS or force_merge) else None
-        if R1 is not None:
-            ro = self._readout_packs()
-            st["merge"] = (ptr(A_["S"][0]), int(A_["S"][0].stride(0)), ptr(A_["WA"][0]), int(A_["WA"][0].stride(0)), K, SW, d.E, d.P,
-                           ptr(ro["Wms"]), ptr(ro["Wmw"]), ptr(p[n_["bpm"]] if d.post_merge else p[n_["bro"]]), ptr(R1), int(R1.stride(0)))
-        st["readout"] = self._readout_step_args(A_["S"][0], A_["WA"][0], K, neglogp=st["neglogp"],
-                                                lm_add=L.get("add_live") if lm is not None else None, R1=R1)
-        # ---- reset: one live hypothesis, replicated over the K rows
-        ctl0 = numpy.zeros((G, 16), numpy.int32)
-        ctl0[:, CTL["nlive"]], ctl0[:, CTL["patience"]] = 1, -1
-        if G > 1:
-            ctl0[:, 8] = limits            # every search's own position limit
-        st["ctl"].copy_(torch.from_numpy(ctl0.reshape(st["ctl"].shape)))
-        st["fctl"].copy_(torch.tensor([1000.0, 0.0, 0.0, 0.0]).repeat(G).view(st["fctl"].shape))
-        st["running"].zero_()
-        st["live_col"].zero_()
-        A_["S"][0].copy_(self._initial_state().unsqueeze(0).expand(K, SW))
-        A_["W"][0].zero_()
-        if d.conv:
-            A_["W"][0][:, 0] = 1.0
-        if pos_needed:
-            A_["pos"].zero_()         # centre of the initial glimpses [1, 0, ...]: mean 0, no median crossing -> 0
-        if on_dev_lm:
-            first = lm.initial_states(K)
-            L["states_live"].copy_(first["states"])
-            L["weights_live"].copy_(first["weights"])
-            L["add_live"].copy_(first["add"])
-        st["on_dev_lm"] = on_dev_lm
-        st["stop_on"] = stop_on
-        # everything the captured launches depend on belongs to the key: the language model's weighting and normalisation flags are
-        # kernel arguments of the readout, its tables and error word are pointers inside the FST walk's argument block
-        lm_key = None if lm is None else (float(lm.lm_weight), float(lm.am_beta), tuple(bool(v) for v in lm.norm), float(getattr(lm, "no_transition_cost", 0.0)))
-        lm_ptrs = () if not on_dev_lm else tuple(sorted((k, t.data_ptr()) for k, t in lm._dev.items())) + (lm._err.data_ptr(),)
-        st["key"] = ("beam_step", K_one, G, Tp, int(max_length), stop_on, int(bool(ignore_first_eol)), int(eol), float(char_discount),
-                     float(round_to_inf), lm is not None, on_dev_lm, lm_key, R1 is not None, self.criterion)
-        st["volatile"] = (g["A"].data_ptr(), g["PA"].data_ptr(), g["Am"].data_ptr(), ws.generation, id(pk), self.store.version, lm_ptrs)
-        self._beam = st
-        return st
+        self.current_search = BeamState(self, K, eol, max_length, ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge)
+        return self.current_search
 
     def _readout_step_args(self, S2, WA2, n, neglogp=None, lm_add=None, uniforms=None, outputs=None, costs=None, logits=None, R1=None):
         """Argument block of the fused generation-time readout + emitter (lvsr_readout_step)."""
@@ -890,63 +758,3 @@ class SequenceGenerator(object):
             R1=R1, ldr1=0 if R1 is None else int(R1.stride(0)), emitter=int(self.mse),
             outputs=outputs, costs=costs, n_hidden=len(self.pm_hidden), Wh=[p[w] for w, _, _ in self.pm_hidden],
             bh=[p[b] for _, b, _ in self.pm_hidden], dimh=[w for _, _, w in self.pm_hidden])
-
-    def beam_costs(self):
-        """Pass A of a position: glimpses of the live hypotheses -> readout -> step costs `neglogp` (K,V)
-        (logprobs_computer, search.py:126-134; with a language model ShallowFusionReadout + LMEmitter)."""
-        d, lib, st = self.d, self.lib, self._beam
-        K, A_ = st["K"], st["A"]
-        lib.call("lvsr_attdec_fwd", lib.stream_for(A_["S"]), ctypes.byref(st["argsA"]), 0)
-        if "merge" in st:
-            lib.call("lvsr_readout_merge", lib.stream_for(st["neglogp"]), *st["merge"])
-        lib.call("lvsr_readout_step", lib.stream_for(st["neglogp"]), ctypes.byref(st["readout"]))
-
-    def beam_select(self):
-        """Stopping rules, the beam_size best continuations, finished hypotheses, back-pointers; gathers the rows of pass B."""
-        st = self._beam
-        self.lib.call("lvsr_beam_select", self.lib.stream_for(st["ctl"]), ctypes.byref(st["args"]))
-
-    def beam_advance(self):
-        """Pass B: glimpses AGAIN on the re-arranged hypotheses (the window of the location prior depends on the batch it is
-        computed for) + compute_states with the chosen characters (next_state_computer, search.py:112-124), language-model
-        transition, then the surviving rows become the new beam."""
-        d, lib, st = self.d, self.lib, self._beam
-        K, B_ = st["rows"], st["B"]
-        # (The language-model walk needs the chosen characters and the gathered state sets, nothing of pass B — and pass B nothing of it.
-        # Run on a second stream beside pass B — fork / join through events, two branches of the step's graph — it was measured in round 6:
-        # 0.94 -> 1.12 ms per utterance at 64 x 4, 0.92 -> 1.18 at 64 x 8.  A fork and a join per position cost more than the 18 us of
-        # pointer chasing they take off the chain; serial.)
-        if "stepB" in st:
-            self._beam_step_run(st)
-        else:
-            if d.embed:          # lookup feedback needs the fork's GEMMs; one-hot feedback was gathered by the select launch
-                self._feedback_forks(st["chars"], K, [(self.n, B_["xg"])], st["fb"])
-            lib.call("lvsr_attdec_fwd", lib.stream_for(B_["S"]), ctypes.byref(st["argsB"]), 0)
-        if st["on_dev_lm"]:
-            self._beam_lm_step(st, K)
-        lib.call("lvsr_beam_compact", lib.stream_for(st["ctl"]), ctypes.byref(st["args"]))
-
-    def _beam_lm_step(self, st, K):
-        """Language-model transition on the chosen characters + look-ahead costs of the new state sets (lvsr_fst_lm_step*)."""
-        lib, L, lm = self.lib, st["lm"], self.language_model
-        grouped = st["groups"] > 1       # the rows of finished searches are skipped (their characters are stale)
-        args = [ctypes.byref(lm._fst), ptr(L["states_sel"]), ptr(L["weights_sel"]), ptr(st["chars"]), K, ptr(L["states_new"]),
-                ptr(L["weights_new"]), ptr(L["add_new"]), ptr(lm._err)] + ([ptr(st["ctl"]), st["K"]] if grouped else [])
-        lib.call("lvsr_fst_lm_step_groups" if grouped else "lvsr_fst_lm_step", lib.stream_for(L["states_sel"]), *args)
-
-    def beam_steps(self, n):
-        """n consecutive positions as ONE replayed hipGraph (the position counter lives on the device, so the graph does not
-        depend on where the search stands): the driver looks at the control block every n positions anyway."""
-        st = self._beam
-
-        def enqueue():
-            for _ in range(n):
-                self.beam_costs()
-                self.beam_select()
-                self.beam_advance()
-        key = st["key"] if n == 1 else (st["key"], "x%d" % n)
-        self.lib.region(self, key, st["ctl"], enabled=self.use_graph, volatile=st["volatile"], drain=False).run(enqueue)
-
-    def beam_step(self):
-        """All launches of one position as one replayed hipGraph (captured on the second step of a search shape)."""
-        self.beam_steps(1)

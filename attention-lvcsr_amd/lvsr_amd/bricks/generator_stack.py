@@ -328,7 +328,7 @@ class StackedSequenceGenerator(SequenceGenerator):
         return dict(accH=accH, accWe=accWe, accEb=accEb, DCV=DCV, dPA=dPA, DWA=DWA,
                     fwd_args=lib.make("lvsr_attdec_args", **att["fields"]))
 
-    # ---- device beam search: pass B (csrc/beam.hip, generator.beam_begin / beam_advance) ---------------------------------
+    # ---- device beam search: pass B (csrc/beam.hip, bricks/beam_state.py: BeamState / BeamState.advance) ------------------
     def _beam_step_blocks(self, pk, g, K, B_, skip_pos, pos_word, tag, groups=0, group_Tp=None):
         att_bufs = {k: B_[k] for k in ("S", "W", "pos", "WA", "EN", "ZB", "sW", "CV", "ep")}
         # the select kernel has moved the position counter on: step0 = -1
@@ -336,9 +336,9 @@ class StackedSequenceGenerator(SequenceGenerator):
                                  broadcast=True, step_dev=pos_word, groups=groups, group_Tp=group_Tp)
 
     def _beam_step_run(self, st):
-        lib, blk = self.lib, st["stepB"]
+        lib, blk = self.lib, st.stepB
         S = blk["att"]["bufs"]["S"]
-        self._feedback_forks(st["chars"], st["rows"], self._layer_xgs(blk), st["fb"])
+        self._feedback_forks(st.chars, st.rows, self._layer_xgs(blk), st.fb)
         self._run_step(blk, 0, lib.stream_for(S))
 
     # ---- free-running generation -----------------------------------------------------------------------------------------

@@ -172,6 +172,8 @@ class FSTLanguageModel(object):
     """`LanguageModel` + `FSTTransition` (language_models.py:14-72,107-137) with the fusion settings of
     `SpeechRecognizer.__init__` (recognizer.py:322-337: weight, normalize_am_weights=True, normalize_lm_weights=False,
     normalize_tot_weights=False, am_beta=1.0 defaults)."""
+    on_device = False        # the walk runs on the host (DeviceFSTLanguageModel: on the device)
+
     def __init__(self, fst, nn_char_map=None, remap_table=None, no_transition_cost=1e12, weight=0.0,
                  normalize_am_weights=True, normalize_lm_weights=False, normalize_tot_weights=False, am_beta=1.0):
         self.fst = fst

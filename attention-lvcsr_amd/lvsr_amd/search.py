@@ -1,4 +1,4 @@
-"""Beam search driver over the device-resident beam step (csrc/beam.hip, `SequenceGenerator.beam_*`).
+"""Beam search driver over the device-resident beam step (csrc/beam.hip, bricks/beam_state.py `BeamState`).
 
 The reference's `BeamSearch.search` (libs/blocks/blocks/search.py:244-407, as modified by lvsr) is a host loop around two
 compiled functions; here the whole position — step costs of every continuation, choice of the `beam_size` best, finished
@@ -11,19 +11,30 @@ Two things need the host inside the loop and switch the driver to one synchronis
 `validate_solution_function` (a Python callback that may veto a finished hypothesis, search.py:372-374) and a language
 model whose walk runs on the host (`FSTLanguageModel` without the device tables).
 """
-import os
-
 import numpy
 import torch
 
-from .bricks.generator import CTL
+from .bricks.beam_state import CTL, HOST_TABLES
 
 POLL_EVERY = 8          # positions between two looks at the `done` word (a look is the only host<->device round trip)
+STOP_ON = ("patience", "optimistic_future_cost")
 
 
 class CandidateNotFoundError(Exception):
     """search.py:15-16"""
-    pass
+
+
+# what a search raises in place of a result (`_raise_device_errors`, `_collect`); a batch reports them utterance by utterance
+SEARCH_ERRORS = (CandidateNotFoundError, AssertionError, RuntimeError, UnboundLocalError)
+
+
+class SearchRun(object):
+    """Handle of a set of searches in flight (`BeamSearch.begin` / `begin_batch`): its device state, how far it has been driven,
+    and the last look at the control blocks (`ctl`, through the pinned block `host` and `event` on a GPU)."""
+    def __init__(self, state, limits, host, first_token, char_discount):
+        self.state, self.limits, self.host, self.first_token, self.char_discount = state, limits, host, first_token, char_discount
+        self.max_length = max(limits)                 # positions to enqueue at the most; every search stops at its own limit
+        self.positions, self.done, self.ctl, self.event = 0, False, None, None
 
 
 class BeamSearch(object):
@@ -50,49 +61,23 @@ class BeamSearch(object):
                round_to_inf=1e9, stop_on="patience", validate_solution_function=None):
         """`input_values` = {'recordings': (T,F) ndarray}.  Returns (outputs, costs) lists, best first, or the padded
         (outputs, mask, step costs) arrays with `as_arrays`."""
-        if stop_on not in ("patience", "optimistic_future_cost"):
+        if stop_on not in STOP_ON:
             raise ValueError("Unknown stopping criterion {}".format(stop_on))
-        rec, gen = self.rec, self.rec.generator
-        lm = gen.language_model
-        host_lm = lm is not None and not getattr(lm, "on_device", False)
-        stepping = host_lm or validate_solution_function is not None
-        max_length = int(max_length)
-        first_token = 0 if lm is not None else gen.d.V            # LMEmitter / SoftmaxEmitter initial outputs
-        if max_length <= 0:
+        lm = self.rec.generator.language_model
+        host_lm = lm if lm is not None and not lm.on_device else None
+        stepping = host_lm is not None or validate_solution_function is not None
+        if int(max_length) <= 0:
             raise CandidateNotFoundError()
+        run = self._begin(lambda: self.rec.compute_contexts(input_values["recordings"]), [max_length], eol_symbol, ignore_first_eol,
+                          char_discount, round_to_inf, stop_on, False, stepping)
         if stepping:
-            with rec._on_stream():
-                rec.compute_contexts(input_values["recordings"])
-                st = gen.beam_begin(self.beam_size, eol_symbol, max_length, ignore_first_eol, char_discount, round_to_inf, stop_on)
-                ctl = self._search_stepping(st, input_values, lm if host_lm else None, validate_solution_function, first_token)
-            return self._finish(st, ctl, first_token, char_discount, as_arrays)
-        run = self.begin(input_values, eol_symbol, max_length, ignore_first_eol=ignore_first_eol, char_discount=char_discount,
-                         round_to_inf=round_to_inf, stop_on=stop_on)
-        while not run["done"]:
+            with self.rec._on_stream():
+                self._search_stepping(run.state, input_values, host_lm, validate_solution_function, run.first_token)
+            run.done = True
+        while not run.done:
             self.advance(run, POLL_EVERY, wait=True)
         return self.finish(run, as_arrays=as_arrays)
 
-    # ---- the same search in pieces that never block the host: several searches (one recognizer + stream each) can be kept in
-    #      flight from one thread (tools/bench_decode.py: decoding is "replicas only", also within a GPU) -----------------------
-    def begin(self, input_values, eol_symbol, max_length, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
-              stop_on="patience", force_merge=False):
-        """Enqueue the encoder pass and the reset of the beam state; returns the handle of the running search."""
-        rec, gen = self.rec, self.rec.generator
-        if stop_on not in ("patience", "optimistic_future_cost"):
-            raise ValueError("Unknown stopping criterion {}".format(stop_on))
-        lm = gen.language_model
-        assert lm is None or getattr(lm, "on_device", False), "the free-running search needs the device language model"
-        with rec._on_stream():
-            rec.compute_contexts(input_values["recordings"])
-            st = gen.beam_begin(self.beam_size, eol_symbol, int(max_length), ignore_first_eol, char_discount, round_to_inf, stop_on,
-                                force_merge=force_merge)
-        host = None
-        if rec.device.type == "cuda":
-            host = torch.empty(16, dtype=torch.int32).pin_memory()
-        return dict(st=st, positions=0, max_length=int(max_length), done=False, ctl=None, host=host, event=None,
-                    first_token=0 if lm is not None else gen.d.V, char_discount=char_discount)
-
-    # ---- several utterances in one set of launches ---------------------------------------------------------------------
     def search_batch(self, recordings, eol_symbol, max_lengths, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
                      stop_on="patience", as_arrays=False, validate_solution_function=None):
         """The searches of N utterances side by side: one encoder pass over the padded batch, then every launch of a position
@@ -103,135 +88,134 @@ class BeamSearch(object):
         A language model walked on the host or a `validate_solution_function` put the host inside every position (module
         docstring): there is nothing to share then, and the utterances are searched one after the other."""
         lm = self.rec.generator.language_model
-        if validate_solution_function is not None or (lm is not None and not getattr(lm, "on_device", False)):
+        if validate_solution_function is not None or (lm is not None and not lm.on_device):
             out = []
             for x, limit in zip(recordings, max_lengths):
                 try:
                     out.append(self.search({"recordings": numpy.asarray(x, numpy.float32)[:, None, :]}, eol_symbol, limit,
                                            ignore_first_eol=ignore_first_eol, as_arrays=as_arrays, char_discount=char_discount,
                                            round_to_inf=round_to_inf, stop_on=stop_on, validate_solution_function=validate_solution_function))
-                except (CandidateNotFoundError, AssertionError, RuntimeError, UnboundLocalError) as e:
+                except SEARCH_ERRORS as e:
                     out.append(e)
             return out
         run = self.begin_batch(recordings, eol_symbol, max_lengths, ignore_first_eol=ignore_first_eol, char_discount=char_discount,
                                round_to_inf=round_to_inf, stop_on=stop_on)
-        while not run["done"]:
+        while not run.done:
             self.advance(run, POLL_EVERY, wait=True)
         return self.finish_batch(run, as_arrays=as_arrays)
 
+    # ---- the same searches in pieces that never block the host: several search sets (one recognizer + stream each) can be kept
+    #      in flight from one thread (tools/bench_decode.py: decoding is "replicas only", also within a GPU) ----------------------
+    def begin(self, input_values, eol_symbol, max_length, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
+              stop_on="patience", force_merge=False):
+        """Enqueue the encoder pass and the reset of the beam state; returns the handle of the running search."""
+        return self._begin(lambda: self.rec.compute_contexts(input_values["recordings"]), [max_length], eol_symbol, ignore_first_eol,
+                           char_discount, round_to_inf, stop_on, force_merge)
+
     def begin_batch(self, recordings, eol_symbol, max_lengths, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
                     stop_on="patience"):
-        rec, gen = self.rec, self.rec.generator
-        if stop_on not in ("patience", "optimistic_future_cost"):
-            raise ValueError("Unknown stopping criterion {}".format(stop_on))
+        """`begin` for N utterances side by side.  A batch of one is the single search with the kernels of the batched one
+        (`force_merge`): the same hypotheses in any batch."""
         if len(recordings) == 1:
-            run = self.begin({"recordings": numpy.asarray(recordings[0], numpy.float32)}, eol_symbol, max_lengths[0],
-                             ignore_first_eol=ignore_first_eol, char_discount=char_discount, round_to_inf=round_to_inf, stop_on=stop_on,
-                             force_merge=True)       # the kernels of the batched search: the same hypotheses in any batch
-            run["single"] = True
-            return run
-        lm = gen.language_model
-        assert lm is None or getattr(lm, "on_device", False), "the batched search needs the device language model"
-        limits = [int(m) for m in max_lengths]
-        with rec._on_stream():
-            rec.compute_contexts_batch(recordings)
-            st = gen.beam_begin(self.beam_size, eol_symbol, [max(m, 1) for m in limits], ignore_first_eol, char_discount, round_to_inf, stop_on)
-        host = None
-        if rec.device.type == "cuda":
-            host = torch.empty(tuple(st["ctl"].shape), dtype=torch.int32).pin_memory()
-        return dict(st=st, positions=0, max_length=max(max(limits), 1), limits=limits, done=False, ctl=None, host=host, event=None,
-                    first_token=0 if lm is not None else gen.d.V, char_discount=char_discount)
+            return self.begin({"recordings": numpy.asarray(recordings[0], numpy.float32)}, eol_symbol, max_lengths[0], ignore_first_eol,
+                              char_discount, round_to_inf, stop_on, force_merge=True)
+        return self._begin(lambda: self.rec.compute_contexts_batch(recordings), max_lengths, eol_symbol, ignore_first_eol,
+                           char_discount, round_to_inf, stop_on, False)
 
-    def finish_batch(self, run, as_arrays=False):
-        """-> one entry per utterance: the result, or the exception the single search raises in its place."""
-        if run.get("single"):
-            try:
-                return [self.finish(run, as_arrays=as_arrays)]
-            except (CandidateNotFoundError, AssertionError, RuntimeError, UnboundLocalError) as e:
-                return [e]
-        rec, gen, st = self.rec, self.rec.generator, run["st"]
-        assert run["done"]
+    def _begin(self, compute_contexts, limits, eol_symbol, ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge,
+               stepping=False):
+        """`stepping`: the host drives every position itself (`_search_stepping`); it takes no looks through a pinned block."""
+        rec, gen = self.rec, self.rec.generator
+        if stop_on not in STOP_ON:
+            raise ValueError("Unknown stopping criterion {}".format(stop_on))
         lm = gen.language_model
-        out, stats = [], []
+        assert stepping or lm is None or lm.on_device, "the free-running search needs the device language model"
+        limits = [int(m) for m in limits]
         with rec._on_stream():
-            if lm is not None and getattr(lm, "on_device", False):
-                lm.check_error()
-            rec.encoder.check_persistent()
-            ctl = st["ctl"].cpu().numpy()
-            host = {k: st[k].cpu().numpy() for k in ("fin_pos", "fin_col", "hist_parent", "hist_char", "hist_cost")}
-            for g in range(st["groups"]):
-                view = {k: torch.from_numpy(v[g]) for k, v in host.items()}
-                try:
-                    if run["limits"][g] <= 0:
-                        raise CandidateNotFoundError()
-                    self._raise_device_errors(ctl[g])
-                    out.append(self._collect(view, ctl[g], run["first_token"], run["char_discount"], as_arrays))
-                except (CandidateNotFoundError, AssertionError, RuntimeError, UnboundLocalError) as e:
-                    out.append(e)
-                stats.append(dict(positions=int(ctl[g][CTL["steps"]]), finished=int(ctl[g][CTL["nfin"]]), done=int(ctl[g][CTL["done"]]),
-                                  reused=int(ctl[g][10])))
-        self.last_stats = dict(positions=max(s["positions"] for s in stats), reused=sum(s["reused"] for s in stats), per_utterance=stats)
-        return out
+            compute_contexts()
+            st = gen.beam_begin(self.beam_size, eol_symbol, limits[0] if len(limits) == 1 else [max(m, 1) for m in limits],
+                                ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge=force_merge)
+        host = torch.empty(tuple(st.ctl.shape), dtype=torch.int32).pin_memory() if rec.device.type == "cuda" and not stepping else None
+        # first token: the LMEmitter's / SoftmaxEmitter's initial outputs
+        return SearchRun(st, limits, host, 0 if lm is not None else gen.d.V, char_discount)
 
     def advance(self, run, positions=POLL_EVERY, wait=False):
         """Enqueue up to `positions` more positions and a look at the control block.  wait=False returns at once; the look is
         picked up by the next call (or by `ready`)."""
-        rec, gen, st = self.rec, self.rec.generator, run["st"]
-        if run["done"]:
+        rec, st = self.rec, run.state
+        if run.done:
             return True
-        if run["event"] is not None:                       # a look is in flight
-            if not wait and not run["event"].query():
+        st.check_current()
+        if run.event is not None:                          # a look is in flight
+            if not wait and not run.event.query():
                 return False
-            run["event"].synchronize()
-            run["event"] = None
-            run["ctl"] = run["host"].numpy().copy()
-            if self._all_done(run["ctl"]) or run["positions"] >= run["max_length"]:
-                run["done"] = True
+            run.event.synchronize()
+            run.event = None
+            run.ctl = run.host.numpy().copy()
+            if self._all_done(run.ctl) or run.positions >= run.max_length:
+                run.done = True
                 return True
         if positions <= 0:
             return False
         with rec._on_stream():
-            n = min(int(positions), run["max_length"] - run["positions"])
+            n = min(int(positions), run.max_length - run.positions)
             if n == POLL_EVERY:
-                gen.beam_steps(n)                          # one graph launch for the whole stretch between two looks
+                st.steps(n)                                # one graph launch for the whole stretch between two looks
             else:
                 for _ in range(n):
-                    gen.beam_step()
-            run["positions"] += n
-            if run["host"] is None:                        # CPU emulator: plain synchronous look
-                run["ctl"] = st["ctl"].cpu().numpy()
-                run["done"] = self._all_done(run["ctl"]) or run["positions"] >= run["max_length"]
-                return run["done"]
-            run["host"].copy_(st["ctl"], non_blocking=True)
-            run["event"] = torch.cuda.Event()
-            run["event"].record(torch.cuda.current_stream(rec.device))
+                    st.steps(1)
+            run.positions += n
+            if run.host is None:                           # CPU emulator: plain synchronous look
+                run.ctl = st.ctl.cpu().numpy()
+                run.done = self._all_done(run.ctl) or run.positions >= run.max_length
+                return run.done
+            run.host.copy_(st.ctl, non_blocking=True)
+            run.event = torch.cuda.Event()
+            run.event.record(torch.cuda.current_stream(rec.device))
         if wait:
-            return self.advance(run, 0, wait=True) if run["event"] is not None else run["done"]
+            return self.advance(run, 0, wait=True) if run.event is not None else run.done
         return False
 
     @staticmethod
-    def _all_done(ctl):
-        """ctl: the control block of one search (16 words) or of a batch of searches (N, 16)."""
-        return bool(numpy.all(numpy.asarray(ctl).reshape(-1, 16)[:, CTL["done"]] != 0))
+    def _all_done(ctl):          # ctl: the control blocks of a search set, (G, 16)
+        return bool(numpy.all(ctl[:, CTL["done"]] != 0))
 
     def finish(self, run, as_arrays=False):
-        """Collect the result of a search whose `advance` reported done."""
-        rec, gen = self.rec, self.rec.generator
-        assert run["done"]
-        lm = gen.language_model
-        with rec._on_stream():
-            if lm is not None and getattr(lm, "on_device", False):
-                lm.check_error()
-            ctl = run["st"]["ctl"].cpu().numpy()
-            return self._finish(run["st"], ctl, run["first_token"], run["char_discount"], as_arrays)
+        """Collect the result of a search whose `advance` reported done; `last_stats` then carries its `finished` and `done` too."""
+        entry = self._finish(run, as_arrays)[0]
+        self.last_stats.update(finished=self.last_stats["per_utterance"][0]["finished"], done=self.last_stats["per_utterance"][0]["done"])
+        if isinstance(entry, Exception):
+            raise entry
+        return entry
 
-    def _finish(self, st, ctl, first_token, char_discount, as_arrays):
-        with self.rec._on_stream():
-            self.rec.encoder.check_persistent()
-            self._raise_device_errors(ctl)
-            self.last_stats = dict(positions=int(ctl[CTL["steps"]]), finished=int(ctl[CTL["nfin"]]), done=int(ctl[CTL["done"]]),
-                                   reused=int(ctl[10]))        # positions whose second attention pass was the first one's results
-            return self._collect(st, ctl, first_token, char_discount, as_arrays)
+    def finish_batch(self, run, as_arrays=False):
+        """-> one entry per utterance: the result, or the exception the single search raises in its place."""
+        return self._finish(run, as_arrays)
+
+    def _finish(self, run, as_arrays):
+        rec, st, lm = self.rec, run.state, self.rec.generator.language_model
+        st.check_current()
+        assert run.done
+        with rec._on_stream():
+            if lm is not None and lm.on_device:
+                lm.check_error()
+            rec.encoder.check_persistent()
+            ctl = st.ctl.cpu().numpy()
+            host = {k: getattr(st, k).cpu().numpy() for k in HOST_TABLES}
+        out, stats = [], []
+        for g in range(st.groups):
+            try:
+                if run.limits[g] <= 0:
+                    raise CandidateNotFoundError()
+                self._raise_device_errors(ctl[g])
+                out.append(self._collect({k: v[g] for k, v in host.items()}, ctl[g], run.first_token, run.char_discount, as_arrays))
+            except SEARCH_ERRORS as e:
+                out.append(e)
+            # reused: positions whose second attention pass was the first one's results
+            stats.append(dict(positions=int(ctl[g][CTL["steps"]]), finished=int(ctl[g][CTL["nfin"]]), done=int(ctl[g][CTL["done"]]),
+                              reused=int(ctl[g][CTL["reused"]])))
+        self.last_stats = dict(positions=max(s["positions"] for s in stats), reused=sum(s["reused"] for s in stats), per_utterance=stats)
+        return out
 
     @staticmethod
     def _raise_device_errors(ctl):
@@ -245,56 +229,54 @@ class BeamSearch(object):
 
     def _search_stepping(self, st, input_values, host_lm, validate, first_token):
         """One synchronisation per position: the host language-model walk feeds the fusion costs of the live hypotheses,
-        and/or a Python callback vetoes finished hypotheses (search.py:372-374)."""
+        and/or a Python callback vetoes finished hypotheses (search.py:372-374).  One search: group 0 of the state."""
         gen, dev = self.rec.generator, self.rec.device
-        K = st["K"]
+        K = st.K
         lm_states = host_lm.initial_states(1) if host_lm is not None else None
         hist_p, hist_c = [], []
-        ctl = st["ctl"].cpu().numpy()
-        for position in range(st["max_length"]):
+        ctl = st.ctl[0].cpu().numpy()
+        for position in range(st.max_length):
             if host_lm is not None:
                 n = int(ctl[CTL["nlive"]])
                 add = numpy.zeros((K, gen.d.V), numpy.float32)
                 if n:
                     add[:n] = lm_states["add"][:n]
                     add[n:] = add[0]
-                st["lm"]["add_live"].copy_(torch.from_numpy(add))
+                st.lm["add_live"].copy_(torch.from_numpy(add))
             # where this position's finished hypotheses will land: in patience mode the kernel first sorts the list and cuts it to K
             nfin_before = int(ctl[CTL["nfin"]])
-            if st["stop_on"] == "patience" and int(ctl[CTL["nlive"]]) > 0:
+            if st.stop_on == "patience" and int(ctl[CTL["nlive"]]) > 0:
                 nfin_before = min(nfin_before, K)
-            gen.beam_costs()
-            gen.beam_select()
-            ctl = st["ctl"].cpu().numpy()
+            st.costs()
+            st.select()
+            ctl = st.ctl[0].cpu().numpy()
             if ctl[CTL["done"]] in (1, 2):
                 break                                         # a stopping rule fired: nothing was selected at this position
             nsel, nlive = int(ctl[CTL["nsel"]]), int(ctl[CTL["nlive"]])
-            parents = st["parents"].cpu().numpy()[:nsel]
-            chars = st["chars"].cpu().numpy()[:nsel]
-            keep = st["keep"].cpu().numpy()[:nlive]
+            parents = st.parents.cpu().numpy()[:nsel]
+            chars = st.chars.cpu().numpy()[:nsel]
+            keep = st.keep.cpu().numpy()[:nlive]
             if validate is not None:
-                hist_p.append(st["hist_parent"][position].cpu().numpy().copy())
-                hist_c.append(st["hist_char"][position].cpu().numpy().copy())
+                hist_p.append(st.hist_parent[0, position].cpu().numpy().copy())
+                hist_c.append(st.hist_char[0, position].cpu().numpy().copy())
                 nfin = int(ctl[CTL["nfin"]])
                 if nfin > nfin_before:
-                    cols = st["fin_col"].cpu().numpy()
+                    cols = st.fin_col[0].cpu().numpy()
                     ok = [i for i in range(nfin_before, nfin)
                           if validate(input_values, self._tokens_of(hist_p, hist_c, position, int(cols[i]), first_token))]
                     if len(ok) != nfin - nfin_before:
-                        for name in ("fin_pos", "fin_col", "fin_cost", "fin_score"):
-                            t = st[name]
+                        for t in (st.fin_pos[0], st.fin_col[0], st.fin_cost[0], st.fin_score[0]):
                             kept = t[torch.as_tensor(ok, dtype=torch.int64, device=dev)].clone() if ok else t[:0]
                             t[nfin_before: nfin_before + len(ok)] = kept
-                        st["ctl"][CTL["nfin"]] = nfin_before + len(ok)
+                        st.ctl[0, CTL["nfin"]] = nfin_before + len(ok)
                         ctl[CTL["nfin"]] = nfin_before + len(ok)
             if host_lm is not None:
                 lm_states = host_lm.take(lm_states, parents)
                 lm_states = host_lm.transition(lm_states, chars)
                 lm_states = host_lm.take(lm_states, keep)
-            gen.beam_advance()
+            st.advance()
             if ctl[CTL["done"]]:
                 break
-        return st["ctl"].cpu().numpy()
 
     @staticmethod
     def _tokens_of(hist_p, hist_c, position, col, first_token):
@@ -304,16 +286,14 @@ class BeamSearch(object):
             col = int(hist_p[p][col])
         return numpy.array([first_token] + toks[::-1])
 
-    def _collect(self, st, ctl, first_token, char_discount, as_arrays):
-        """Follow the back-pointers of the finished hypotheses and rank them (search.py:378-407)."""
+    def _collect(self, host, ctl, first_token, char_discount, as_arrays):
+        """Follow the back-pointers of the finished hypotheses of one search and rank them (search.py:378-407).  `host`: host
+        copies of its `HOST_TABLES`, `ctl`: of its control block."""
         nfin, npos = int(ctl[CTL["nfin"]]), int(ctl[CTL["steps"]])
         if nfin == 0:
             raise CandidateNotFoundError()
-        fin_pos = st["fin_pos"][:nfin].cpu().numpy()
-        fin_col = st["fin_col"][:nfin].cpu().numpy()
-        hp = st["hist_parent"][:npos].cpu().numpy()
-        hc = st["hist_char"][:npos].cpu().numpy()
-        hcost = st["hist_cost"][:npos].cpu().numpy()
+        fin_pos, fin_col = host["fin_pos"][:nfin], host["fin_col"][:nfin]
+        hp, hc, hcost = host["hist_parent"][:npos], host["hist_char"][:npos], host["hist_cost"][:npos]
         hyps = []
         for p, col in zip(fin_pos, fin_col):
             toks, run = [], []

@@ -13,14 +13,14 @@ for mode in ("graph", "eager"):
         rec.compute_contexts(x[:, None, :])
         st = gen.beam_begin(16, rec.eos_label, 266, False, 1.0, 1e9, "optimistic_future_cost")
         for _ in range(4):
-            gen.beam_step()
+            st.steps()
         torch.cuda.synchronize()
         N = 64
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         e0.record()
         for _ in range(N):
-            gen.beam_step()
+            st.steps()
         e1.record()
         t1 = time.perf_counter()
         torch.cuda.synchronize()
