@@ -646,6 +646,18 @@ __global__ __launch_bounds__(256) void enc_pbwd_h0_kernel(const float* dh, int B
     for (int b = 0; b < B; ++b) s += dh[((size_t)dir * Bp + b) * H + j];
     (dir == 0 ? out_f : out_b)[j] = s;
 }
+// the same sums for several layers in one launch (blockIdx.y = layer): behind the last BPTT launch of a backward pass
+#define H0_MANY_MAX 16
+struct H0Pack { lvsr_h0_desc d[H0_MANY_MAX]; };
+__global__ __launch_bounds__(256) void enc_pbwd_h0_many_kernel(H0Pack pk) {
+    const lvsr_h0_desc& d = pk.d[blockIdx.y];
+    const int dir = blockIdx.z;
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= d.H) return;
+    float s = 0.f;
+    for (int b = 0; b < d.B; ++b) s += d.dh[((size_t)dir * d.Bp + b) * d.H + j];
+    (dir == 0 ? d.out_f : d.out_b)[j] = s;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // Unit-blocked forward kernel (one utterance per cluster): a group of G = 16 U lanes serves U units, lane q of the group keeps the KS
@@ -891,7 +903,8 @@ int lvsr_bigru_fwd_persistent(hipStream_t s, const EncFwd& a0, int use_graph) {
         // planes and XCC_ID granules only: the abort word (first 256 bytes) is STICKY — no launch clears it, so a cluster that gave
         // up in the forward pass of a step is still reported after the backward pass (which shares this workspace) and after any
         // number of replayed steps; the host clears it when it has raised (Encoder.check_persistent)
-        (void)hipMemsetAsync(planes, 0, bytes, s);
+        // (persistent & 4: the caller has cleared them, lvsr_clear_many at the head of its step)
+        if (!(a.persistent & 4)) (void)hipMemsetAsync(planes, 0, bytes, s);
         switch (g.KSPLIT / (g.NTH / 256)) {
             case 2: launch_fwd<64, 2>(s, a, g, planes, hello, ab, flags); break;
             case 4: launch_fwd<64, 4>(s, a, g, planes, hello, ab, flags); break;
@@ -917,13 +930,16 @@ int lvsr_bigru_bwd_persistent(hipStream_t s, const EncBwd0& a, int use_graph) {
     float* dh = a.dh_ws;
     const int flags = persist_flags();
     auto enqueue = [&]() {
-        (void)hipMemsetAsync(planes, 0, bytes, s);          // not the abort word: sticky until the host has seen it (see the forward)
+        // not the abort word: sticky until the host has seen it (see the forward)
+        if (!(a.persistent & 4)) (void)hipMemsetAsync(planes, 0, bytes, s);
         switch (g.KSPLIT / (g.NTH / 256)) {
             case 2: launch_bwd<64, 2>(s, a, g, planes, hello, ab, dh, Bp, flags); break;
             case 4: launch_bwd<64, 4>(s, a, g, planes, hello, ab, dh, Bp, flags); break;
             default: launch_bwd<64, 8>(s, a, g, planes, hello, ab, dh, Bp, flags); break;
         }
-        hipLaunchKernelGGL(enc_pbwd_h0_kernel, dim3((a.H + 255) / 256, 1, 2), dim3(256), 0, s, dh, Bp, a.B, a.H, a.dh0[0], a.dh0[1]);
+        // (persistent & 2: the caller sums the initial-state gradients of all its layers in one lvsr_bigru_h0_many launch)
+        if (!(a.persistent & 2))
+            hipLaunchKernelGGL(enc_pbwd_h0_kernel, dim3((a.H + 255) / 256, 1, 2), dim3(256), 0, s, dh, Bp, a.B, a.H, a.dh0[0], a.dh0[1]);
     };
     GraphKey key("bigru_pbwd");
     key.add(&a, sizeof(a));
@@ -931,4 +947,22 @@ int lvsr_bigru_bwd_persistent(hipStream_t s, const EncBwd0& a, int use_graph) {
     key.add(&g.NTH, sizeof(g.NTH));
     key.add(&flags, sizeof(flags));
     return lvsr_run_graph(s, use_graph, key, enqueue, "lvsr_bigru_bwd(persistent)");
+}
+
+extern "C" int lvsr_bigru_h0_many(void* stream, const lvsr_h0_desc* descs, int n) {
+    LVSR_REQUIRE(n >= 0 && (n == 0 || descs), "lvsr_bigru_h0_many: bad arguments");
+    for (int i = 0; i < n; ++i)
+        LVSR_REQUIRE(descs[i].dh && descs[i].out_f && descs[i].out_b && descs[i].B > 0 && descs[i].H > 0 && descs[i].Bp >= descs[i].B,
+                     "lvsr_bigru_h0_many: bad descriptor %d", i);
+    for (int i0 = 0; i0 < n; i0 += H0_MANY_MAX) {
+        H0Pack pk;
+        const int m = n - i0 < H0_MANY_MAX ? n - i0 : H0_MANY_MAX;
+        int maxH = 0;
+        for (int i = 0; i < H0_MANY_MAX; ++i) {
+            pk.d[i] = descs[i0 + (i < m ? i : 0)];
+            if (i < m && pk.d[i].H > maxH) maxH = pk.d[i].H;
+        }
+        hipLaunchKernelGGL(enc_pbwd_h0_many_kernel, dim3((maxH + 255) / 256, m, 2), dim3(256), 0, (hipStream_t)stream, pk);
+    }
+    return lvsr_check_launch("lvsr_bigru_h0_many");
 }

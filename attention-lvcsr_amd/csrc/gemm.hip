@@ -685,7 +685,7 @@ __global__ __launch_bounds__(256) void lvsr_colsum_finish(const float* part, int
 }
 
 // out[c*rows + r] = in[r*cols + c]
-#define COPY_MANY_MAX 32
+#define COPY_MANY_MAX 64          // (40-byte descriptors: a 2.5 KB kernel argument)
 struct CopyPack { lvsr_copy_desc d[COPY_MANY_MAX]; int n; };
 // blockIdx.y = descriptor; the blocks of a descriptor stride over its rows, the threads over 16-byte pieces of a row
 __global__ __launch_bounds__(256) void lvsr_copy2d_many_kernel(CopyPack pk) {
@@ -707,6 +707,25 @@ __global__ __launch_bounds__(256) void lvsr_copy2d_many_kernel(CopyPack pk) {
             for (int c = threadIdx.x; c < d.cols; c += 256) o[c] = s[c];
         }
     }
+}
+
+// Zero up to CLEAR_MANY_MAX byte ranges in one launch (blockIdx.y = range): bytes up to the first 16-byte boundary and behind the last
+// one singly (work-group 0 of the range), 16-byte stores between them.
+#define CLEAR_MANY_MAX 64
+struct ClearPack { lvsr_clear_desc d[CLEAR_MANY_MAX]; };
+__global__ __launch_bounds__(256) void lvsr_clear_many_kernel(ClearPack pk) {
+    char* p = (char*)pk.d[blockIdx.y].ptr;
+    const long long n = pk.d[blockIdx.y].bytes;
+    long long head = (long long)((16 - ((size_t)p & 15)) & 15);
+    if (head > n) head = n;
+    const long long body = (n - head) / 16, tail = head + body * 16;
+    if (blockIdx.x == 0) {
+        if ((long long)threadIdx.x < head) p[threadIdx.x] = 0;
+        if ((long long)threadIdx.x < n - tail) p[tail + threadIdx.x] = 0;
+    }
+    float4* q = (float4*)(p + head);
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < body; i += (long long)gridDim.x * 256)
+        q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
 __global__ __launch_bounds__(256) void lvsr_transpose_kernel(const float* in, int rows, int cols, float* out) {
@@ -782,7 +801,11 @@ static int sgemm_launch(void* stream, int transA, int transB, int M, int N, int 
     // short, where the last, partly filled round costs more than the smaller tile's lower arithmetic intensity
     // (profiles/r03_gemm_sweep.txt: 6400 x 1536 x 512 122 -> 98 us, 12800 x 512 x 1536 NT 229 -> 200 us; 4096^3 loses 3%).
     const int mid_max = lvsr_knob(LVSR_KNOB_GEMM_MID_TILES) > 0 ? lvsr_knob(LVSR_KNOB_GEMM_MID_TILES) : 2048;
-    const bool mid = big && batch == 1 && (tiles < 256 || (tiles < mid_max && K <= 2048));
+    // A batched call counts the 128-tiles of all its members (grid.z = batch): the decoder's per-utterance products (QR: 100 x 200
+    // x 512, 16 of them = 32 work-groups; dA: 200 x 512 x 100 = 128) filled an eighth and a half of the chip as 128-tiles.  Both
+    // tile kernels contract over k in ascending order, two per MFMA (gemm2_col), so the choice moves no bit.
+    const long long units = (long long)tiles * batch;
+    const bool mid = big && (units < 256 || (units < mid_max && K <= 2048));
     if (mid) { tm = 64; tn = 64; tiles = ((M + 63) / 64) * ((N + 63) / 64); }
     g.kchunk = ((K + tk - 1) / tk) * tk;
     if (g.kchunk == 0) g.kchunk = tk;
@@ -985,6 +1008,26 @@ int lvsr_copy2d_many(void* stream, const lvsr_copy_desc* descs, int n) {
         hipLaunchKernelGGL(lvsr_copy2d_many_kernel, dim3(128, pk.n), dim3(256), 0, (hipStream_t)stream, pk);
     }
     return lvsr_check_launch("lvsr_copy2d_many");
+}
+
+int lvsr_clear_many(void* stream, const lvsr_clear_desc* descs, int n) {
+    LVSR_REQUIRE(n >= 0 && (n == 0 || descs), "lvsr_clear_many: bad arguments");
+    for (int i = 0; i < n; ++i)
+        LVSR_REQUIRE(descs[i].bytes >= 0 && (descs[i].bytes == 0 || descs[i].ptr), "lvsr_clear_many: bad descriptor %d", i);
+    for (int i0 = 0; i0 < n; i0 += CLEAR_MANY_MAX) {
+        ClearPack pk;
+        const int m = n - i0 < CLEAR_MANY_MAX ? n - i0 : CLEAR_MANY_MAX;
+        long long most = 0;
+        for (int i = 0; i < CLEAR_MANY_MAX; ++i) {
+            pk.d[i] = descs[i0 + (i < m ? i : 0)];
+            if (i < m && pk.d[i].bytes > most) most = pk.d[i].bytes;
+        }
+        // (16 KB per work-group and trip; at most 64 work-groups per range)
+        long long gx = (most + 16383) / 16384;
+        gx = gx < 1 ? 1 : gx > 64 ? 64 : gx;
+        hipLaunchKernelGGL(lvsr_clear_many_kernel, dim3((unsigned)gx, m), dim3(256), 0, (hipStream_t)stream, pk);
+    }
+    return lvsr_check_launch("lvsr_clear_many");
 }
 
 int lvsr_transpose(void* stream, const float* in, int rows, int cols, float* out) {

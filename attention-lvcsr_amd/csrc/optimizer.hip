@@ -38,8 +38,11 @@ __global__ __launch_bounds__(256) void opt_sqnorm_kernel(Opt o) {
 }
 
 // scratch[0] = gradient norm, scratch[1] = StepClipping multiplier
-__global__ __launch_bounds__(256) void opt_norm_kernel(Opt o, int nparts) {
+// (clear_flags: the sequence whose rules and max-norm kernels raise the non-finite flags themselves clears them here, one launch
+// ahead of every raise; a guarded step leaves them as they are)
+__global__ __launch_bounds__(256) void opt_norm_kernel(Opt o, int nparts, int clear_flags) {
     __shared__ float red[4];
+    __shared__ int skipped;
     float s = 0.f;
     for (int i = threadIdx.x; i < nparts; i += 256) s += o.scratch[2 + i];
     s = blk_sum256(s, red);
@@ -72,37 +75,64 @@ __global__ __launch_bounds__(256) void opt_norm_kernel(Opt o, int nparts) {
             }
         }
         o.scratch[2] = burn;                                           // the partial sums are consumed
+        skipped = skip ? 1 : 0;
+    }
+    if (clear_flags) {
+        __syncthreads();
+        if (!skipped)
+            for (int sgi = threadIdx.x; sgi < o.nseg; sgi += 256) o.segflag[sgi] = 0;
     }
 }
 
-// clipping multiplier, Scale, BasicMomentum, AdaDelta -> step
+// clipping multiplier, Scale, BasicMomentum, AdaDelta for element i: updates the rule state, -> its step
+__device__ __forceinline__ float opt_rule_step(const Opt& o, long long i, float mult) {
+    float s = o.grad[i] * o.grad_scale * mult;
+    if (o.use_momentum) {
+        s = o.learning_rate * s;
+        s = o.momentum * o.velocity[i] + s;
+        o.velocity[i] = s;
+    }
+    if (o.use_adadelta) {
+        const float ms = o.decay_rate * o.ms_step[i] + (1.f - o.decay_rate) * s * s;
+        const float dx = sqrtf(o.ms_dx[i] + o.epsilon) / sqrtf(ms + o.epsilon) * s;
+        o.ms_step[i] = ms;
+        o.ms_dx[i] = o.decay_rate * o.ms_dx[i] + (1.f - o.decay_rate) * dx * dx;
+        s = dx;
+    }
+    return s;
+}
+
+// RemoveNotFinite inside the kernels that make the steps (the default sequence): a step that is not finite raises the flag of the
+// segment that holds it — found by a walk over the segment table, which only such an element pays for.  segflag is cleared one
+// launch ahead, by opt_norm_kernel.  Against opt_finite_kernel's test of partial SUMS: a non-finite element shows either way; finite
+// steps whose sum overflows float32 do not show here.
+__device__ __forceinline__ bool opt_not_finite(float s) { return s != s || s - s != 0.f; }
+__device__ void opt_raise(const Opt& o, long long i) {
+    for (int sg = 0; sg < o.nseg; ++sg) {
+        const long long* seg = o.segments + 4 * (long long)sg;
+        if (i >= seg[0] && i < seg[0] + seg[1] * seg[2]) o.segflag[sg] = 1;
+    }
+}
+
+template <bool RAISE>
 __global__ __launch_bounds__(256) void opt_rules_kernel(Opt o) {
     if (o.scratch[3] != 0.f) return;                                   // guarded step: rule state untouched
     const float mult = o.scratch[1];
-    if (blockIdx.x == 0)
+    if (!RAISE && blockIdx.x == 0)
         for (int sgi = threadIdx.x; sgi < o.nseg; sgi += 256) o.segflag[sgi] = 0;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < o.n; i += (long long)gridDim.x * 256) {
-        float s = o.grad[i] * o.grad_scale * mult;
-        if (o.use_momentum) {
-            s = o.learning_rate * s;
-            s = o.momentum * o.velocity[i] + s;
-            o.velocity[i] = s;
-        }
-        if (o.use_adadelta) {
-            const float ms = o.decay_rate * o.ms_step[i] + (1.f - o.decay_rate) * s * s;
-            const float dx = sqrtf(o.ms_dx[i] + o.epsilon) / sqrtf(ms + o.epsilon) * s;
-            o.ms_step[i] = ms;
-            o.ms_dx[i] = o.decay_rate * o.ms_dx[i] + (1.f - o.decay_rate) * dx * dx;
-            s = dx;
-        }
+        const float s = opt_rule_step(o, i, mult);
         o.step[i] = s;
+        if (RAISE && o.remove_not_finite && opt_not_finite(s)) opt_raise(o, i);
     }
 }
 
 // VariableClipping(axis=0) on flagged (rows x cols) segments.  Block (x, seg): 64 columns x 16 row groups (1024 threads: the
 // kernel is a latency chain of strided loads, so 16 rows of a column are in flight at once instead of 4: 97 -> ~25 us); the
 // column norms of (param - step) are folded through LDS in a fixed order, then the same threads rescale their rows.
+// (RAISE: a rescaled step that is not finite — a parameter that is not — raises the segment's flag, as the rules kernel does)
 #define MAXNORM_GROUPS 16
+template <bool RAISE>
 __global__ __launch_bounds__(64 * MAXNORM_GROUPS) void opt_maxnorm_kernel(Opt o) {
     __shared__ float red[MAXNORM_GROUPS][64];
     const long long* seg = o.segments + 4 * (long long)blockIdx.y;
@@ -128,7 +158,9 @@ __global__ __launch_bounds__(64 * MAXNORM_GROUPS) void opt_maxnorm_kernel(Opt o)
         const float k = o.max_norm / norm;
         for (long long r = g; r < rows; r += MAXNORM_GROUPS) {
             const long long x = off + r * cols + j;
-            o.step[x] = o.param[x] - k * (o.param[x] - o.step[x]);
+            const float st = o.param[x] - k * (o.param[x] - o.step[x]);
+            o.step[x] = st;
+            if (RAISE && o.remove_not_finite && opt_not_finite(st)) o.segflag[blockIdx.y] = 1;
         }
     }
 }
@@ -194,12 +226,20 @@ extern "C" int lvsr_opt_step(void* stream, const lvsr_opt_args* args) {
     int nb = (int)((o.n + 255) / 256);
     if (nb > 2048) nb = 2048;
     hipLaunchKernelGGL(opt_sqnorm_kernel, dim3(nparts), dim3(256), 0, s, o);
-    hipLaunchKernelGGL(opt_norm_kernel, dim3(1), dim3(256), 0, s, o, nparts);
-    hipLaunchKernelGGL(opt_rules_kernel, dim3(nb), dim3(256), 0, s, o);
-    if (o.max_norm > 0.f)
-        hipLaunchKernelGGL(opt_maxnorm_kernel, dim3((o.max_cols + 63) / 64, o.nseg), dim3(64 * MAXNORM_GROUPS), 0, s, o);
-    if (o.remove_not_finite)
-        hipLaunchKernelGGL(opt_finite_kernel, dim3(16, o.nseg), dim3(256), 0, s, o);
-    hipLaunchKernelGGL(opt_apply_kernel, dim3(16, o.nseg), dim3(256), 0, s, o);
+    // The kernels that make the steps test them for RemoveNotFinite as they go, and the flags are cleared by the norm kernel
+    // (LVSR_KNOB_OPT_UNFUSED = 1: the rules kernel clears them and a pass of its own over `step` tests partial sums).  The apply
+    // kernel is element-wise: 64 instead of 16 work-groups per segment (the large tensors were 64 trips per thread).
+    const bool raise = !lvsr_knob(LVSR_KNOB_OPT_UNFUSED);
+    hipLaunchKernelGGL(opt_norm_kernel, dim3(1), dim3(256), 0, s, o, nparts, raise ? 1 : 0);
+    const dim3 mgrid((o.max_cols + 63) / 64, o.nseg);
+    if (raise) {
+        hipLaunchKernelGGL(opt_rules_kernel<true>, dim3(nb), dim3(256), 0, s, o);
+        if (o.max_norm > 0.f) hipLaunchKernelGGL(opt_maxnorm_kernel<true>, mgrid, dim3(64 * MAXNORM_GROUPS), 0, s, o);
+    } else {
+        hipLaunchKernelGGL(opt_rules_kernel<false>, dim3(nb), dim3(256), 0, s, o);
+        if (o.max_norm > 0.f) hipLaunchKernelGGL(opt_maxnorm_kernel<false>, mgrid, dim3(64 * MAXNORM_GROUPS), 0, s, o);
+        if (o.remove_not_finite) hipLaunchKernelGGL(opt_finite_kernel, dim3(16, o.nseg), dim3(256), 0, s, o);
+    }
+    hipLaunchKernelGGL(opt_apply_kernel, dim3(raise ? 64 : 16, o.nseg), dim3(256), 0, s, o);
     return lvsr_check_launch("lvsr_opt_step");
 }

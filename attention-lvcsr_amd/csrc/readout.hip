@@ -10,10 +10,11 @@
 #include "lvsr_hip.h"
 
 // out[r, :] = table[idx[r], :] (+ bias)
-__global__ __launch_bounds__(256) void gather_rows_kernel(const float* table, int ldt, const long long* idx, int n,
-                                                          int nrows, int width, const float* bias, float* out, int ldo) {
+// (bx: the work-group's block of 256 columns)
+__device__ __forceinline__ void gather_rows_block(const float* table, int ldt, const long long* idx, int n, int nrows, int width,
+                                                  const float* bias, float* out, int ldo, int bx) {
     const int r = blockIdx.y;
-    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int c = bx * 256 + threadIdx.x;
     if (r >= n || c >= width) return;
     long long v = idx[r];
     float x = 0.f;
@@ -21,17 +22,30 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const float* table, in
     if (bias) x += bias[c];
     out[(size_t)r * ldo + c] = x;
 }
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* table, int ldt, const long long* idx, int n,
+                                                          int nrows, int width, const float* bias, float* out, int ldo) {
+    gather_rows_block(table, ldt, idx, n, nrows, width, bias, out, ldo, blockIdx.x);
+}
+// Two gathers by one index list in one launch (the two fork matrices of a one-hot feedback): the first ceil(width / 256) column
+// blocks serve table a, the others table b.
+struct GatherPart { const float* table; const float* bias; float* out; int ldt, width, ldo; };
+__global__ __launch_bounds__(256) void gather_rows_pair_kernel(GatherPart a, GatherPart b, const long long* idx, int n, int nrows) {
+    const int na = (a.width + 255) / 256;
+    const bool first = (int)blockIdx.x < na;
+    const GatherPart& g = first ? a : b;
+    gather_rows_block(g.table, g.ldt, idx, n, nrows, g.width, g.bias, g.out, g.ldo, first ? blockIdx.x : blockIdx.x - na);
+}
 
 // dst[v, :] = beta*dst[v, :] + sum_{r : idx[r] == v} src[r, :]   (fixed r order: deterministic).  The index list is staged in
 // LDS a chunk at a time and compacted to the rows that hit v, so a thread walks ~n/V matching rows instead of n dependent
 // global index loads (98 -> ~10 us for the 1 600 labels of a WSJ-base minibatch).
 #define SCATTER_CHUNK 2048
-__global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* src, int lds, const long long* idx, int n,
-                                                               int width, float* dst, int ldd, float beta) {
+__device__ __forceinline__ void scatter_add_rows_block(const float* src, int lds, const long long* idx, int n, int width, float* dst,
+                                                       int ldd, float beta, int bx) {
     __shared__ int hit[SCATTER_CHUNK];
     __shared__ int nhit;
     const int v = blockIdx.y;
-    const int c = blockIdx.x * 256 + threadIdx.x;
+    const int c = bx * 256 + threadIdx.x;
     float s = 0.f;
     for (int r0 = 0; r0 < n; r0 += SCATTER_CHUNK) {
         const int m = min(SCATTER_CHUNK, n - r0);
@@ -61,6 +75,19 @@ __global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* src,
         float* d = dst + (size_t)v * ldd + c;
         *d = (beta != 0.f ? beta * *d : 0.f) + s;
     }
+}
+__global__ __launch_bounds__(256) void scatter_add_rows_kernel(const float* src, int lds, const long long* idx, int n,
+                                                               int width, float* dst, int ldd, float beta) {
+    scatter_add_rows_block(src, lds, idx, n, width, dst, ldd, beta, blockIdx.x);
+}
+// Two scatter-adds by one index list in one launch (column blocks as in gather_rows_pair_kernel); per output element the same
+// rows in the same order as the single form.
+struct ScatterPart { const float* src; float* dst; int lds, width, ldd; float beta; };
+__global__ __launch_bounds__(256) void scatter_add_rows_pair_kernel(ScatterPart a, ScatterPart b, const long long* idx, int n) {
+    const int na = (a.width + 255) / 256;
+    const bool first = (int)blockIdx.x < na;
+    const ScatterPart& g = first ? a : b;
+    scatter_add_rows_block(g.src, g.lds, idx, n, g.width, g.dst, g.ldd, g.beta, first ? blockIdx.x : blockIdx.x - na);
 }
 
 // kind: 0 identity, 1 maxout(2 pieces, adjacent pairs), 2 rectifier, 3 tanh
@@ -485,6 +512,35 @@ int lvsr_scatter_add_rows(void* stream, const float* src, int lds, const long lo
     hipLaunchKernelGGL(scatter_add_rows_kernel, dim3((width + 255) / 256, nrows), dim3(256), 0, (hipStream_t)stream, src, lds,
                        idx, n, width, dst, ldd, beta);
     return lvsr_check_launch("lvsr_scatter_add_rows");
+}
+
+int lvsr_gather_rows_pair(void* stream, const long long* idx, int n, int nrows, const float* table_a, int ldt_a, int width_a,
+                          const float* bias_a, float* out_a, int ldo_a, const float* table_b, int ldt_b, int width_b,
+                          const float* bias_b, float* out_b, int ldo_b) {
+    if (n <= 0 || (width_a <= 0 && width_b <= 0)) return LVSR_OK;
+    LVSR_REQUIRE(width_a >= 0 && width_b >= 0 && idx && (width_a == 0 || (table_a && out_a)) && (width_b == 0 || (table_b && out_b)),
+                 "lvsr_gather_rows_pair: bad arguments");
+    LVSR_REQUIRE(n <= GRID_Y_MAX, "lvsr_gather_rows_pair: n = %d rows exceed the %d of one launch (one work-group row per output row)", n,
+                 GRID_Y_MAX);
+    const GatherPart a = {table_a, bias_a, out_a, ldt_a, width_a, ldo_a}, b = {table_b, bias_b, out_b, ldt_b, width_b, ldo_b};
+    hipLaunchKernelGGL(gather_rows_pair_kernel, dim3((width_a + 255) / 256 + (width_b + 255) / 256, n), dim3(256), 0,
+                       (hipStream_t)stream, a, b, idx, n, nrows);
+    return lvsr_check_launch("lvsr_gather_rows_pair");
+}
+
+int lvsr_scatter_add_rows_pair(void* stream, const long long* idx, int n, int nrows, const float* src_a, int lds_a, int width_a,
+                               float* dst_a, int ldd_a, float beta_a, const float* src_b, int lds_b, int width_b, float* dst_b,
+                               int ldd_b, float beta_b) {
+    if (nrows <= 0 || (width_a <= 0 && width_b <= 0)) return LVSR_OK;
+    LVSR_REQUIRE(width_a >= 0 && width_b >= 0 && (n <= 0 || idx) && (width_a == 0 || (src_a && dst_a)) &&
+                 (width_b == 0 || (src_b && dst_b)), "lvsr_scatter_add_rows_pair: bad arguments");
+    LVSR_REQUIRE(nrows <= GRID_Y_MAX,
+                 "lvsr_scatter_add_rows_pair: nrows = %d rows exceed the %d of one launch (one work-group row per destination row)", nrows,
+                 GRID_Y_MAX);
+    const ScatterPart a = {src_a, dst_a, lds_a, width_a, ldd_a, beta_a}, b = {src_b, dst_b, lds_b, width_b, ldd_b, beta_b};
+    hipLaunchKernelGGL(scatter_add_rows_pair_kernel, dim3((width_a + 255) / 256 + (width_b + 255) / 256, nrows), dim3(256), 0,
+                       (hipStream_t)stream, a, b, idx, n);
+    return lvsr_check_launch("lvsr_scatter_add_rows_pair");
 }
 
 int lvsr_act_fwd(void* stream, int kind, const float* x, int ldx, int n, int P, float* y, int ldy) {

@@ -100,6 +100,10 @@ class Encoder(object):
         # (round 6, tools/probes/cu_partition_probe.py: the side stream created with hipExtStreamCreateWithCUMask on its own CUs and the
         # clusters on the others — eager launches only, a hipGraph kernel node has no CU-mask attribute: profiles/r06_cu_partition.md)
         self.overlap = False        # measured and rejected (comment above); the attribute keeps the second-stream code reachable for probes
+        # A forward pass that saves for a backward pass clears the granule planes of ALL its persistent launches, the BPTT ones
+        # included, in one launch in front of the first layer (`_clear_planes`; a memset node in front of every launch otherwise:
+        # 8 x 4.7 us of a WSJ-base step).  False: every launch clears its own (what a pass that saves nothing always does).
+        self.preclear = True
         self._side = None
         self._side_pending = False
 
@@ -141,26 +145,54 @@ class Encoder(object):
             self._packs = packs
         return self._packs[i]
 
+    def _fork_cat_pairs(self, i):
+        """-> (entry of `_cats`, the copies that fill it): the four input-projection matrices of layer i side by side, (I, 6H) =
+        [Wi_f | Wg_f | Wi_b | Wg_b] in the column order of `xg`, and their biases (6H): ONE GEMM per layer produces all input
+        projections of both directions (and one its input gradient) instead of four."""
+        p, ws = self.store.p, self.ws
+        H, I = self.d.Hs[i], self.d.layer_input_dim(i)
+        W = ws.get("enc%d.Wcat" % i, (I, 6 * H))
+        b = ws.get("enc%d.bcat" % i, (6 * H,))
+        pairs = []
+        for di, direction in enumerate(("forward", "backward")):
+            n = self._names(i, direction)
+            o = di * 3 * H
+            pairs += [(p[n["Wi"]], W[:, o: o + H]), (p[n["Wg"]], W[:, o + H: o + 3 * H]),
+                      (p[n["bi"]], b[o: o + H]), (p[n["bg"]], b[o + H: o + 3 * H])]
+        return dict(version=self.store.version, W=W, b=b), pairs
+
     def _fork_cat(self, i):
-        """The four input-projection matrices of layer i side by side, (I, 6H) = [Wi_f | Wg_f | Wi_b | Wg_b] in the column order
-        of `xg`, and their biases (6H): ONE GEMM per layer produces all input projections of both directions (and one its
-        input gradient) instead of four.  Refreshed when the parameters changed (copies, no arithmetic)."""
+        """The concatenated fork weights and biases of layer i (`_fork_cat_pairs`), refreshed when the parameters changed (copies, no
+        arithmetic)."""
         ent = self._cats.get(i)
         if ent is None or ent["version"] != self.store.version or self.lib.capturing:
-            p, ws = self.store.p, self.ws
-            H, I = self.d.Hs[i], self.d.layer_input_dim(i)
-            W = ws.get("enc%d.Wcat" % i, (I, 6 * H))
-            b = ws.get("enc%d.bcat" % i, (6 * H,))
-            pairs = []
-            for di, direction in enumerate(("forward", "backward")):
-                n = self._names(i, direction)
-                o = di * 3 * H
-                pairs += [(p[n["Wi"]], W[:, o: o + H]), (p[n["Wg"]], W[:, o + H: o + 3 * H]),
-                          (p[n["bi"]], b[o: o + H]), (p[n["bg"]], b[o + H: o + 3 * H])]
+            ent, pairs = self._fork_cat_pairs(i)
             self.lib.copy_many(pairs)                      # one launch instead of eight copy kernels
-            ent = dict(version=self.store.version, W=W, b=b)
             self._cats[i] = ent
         return ent["W"], ent["b"]
+
+    def _layer_inputs(self, m, T, B):
+        """What the layers of a forward pass copy from the parameters and the input mask, in ONE launch in front of the first layer
+        (a launch per layer and a copy kernel per subsampled mask before): the concatenated fork weights of every layer whose copy is
+        stale (`_fork_cat`), and the mask of every subsampling layer's output — rows 0, s, 2s, ... of the input mask, s = the product of
+        the subsampling factors so far.  -> [that mask or None] per layer."""
+        d, ws = self.d, self.ws
+        pairs = []
+        for i in range(d.n_layers):
+            ent = self._cats.get(i)
+            if ent is None or ent["version"] != self.store.version or self.lib.capturing:
+                self._cats[i], fresh = self._fork_cat_pairs(i)
+                pairs += fresh
+        masks, stride = [], 1
+        for i, s in enumerate(d.subsample):
+            T = (T + s - 1) // s
+            stride *= s
+            masks.append(None)
+            if m is not None and s > 1:
+                masks[i] = ws.get(self._n(i, "msub"), (T, B))
+                pairs.append((m[::stride], masks[i]))
+        self.lib.copy_many(pairs)
+        return masks
 
     @contextlib.contextmanager
     def _side_stream(self):
@@ -183,9 +215,10 @@ class Encoder(object):
             torch.cuda.current_stream().wait_stream(self._side)
             self._side_pending = False
 
-    def _sync_ws(self, i, B, H):
+    def _sync_ws(self, i, B, H, bwd=False):
         """Scratch of the persistent cluster kernel (granule planes + abort word), or None when the layer runs as
-        per-step kernels (emulator, or a cluster that does not fit the chip)."""
+        per-step kernels (emulator, or a cluster that does not fit the chip).  bwd: a second one of the same size, the BPTT launch's
+        own when the planes are cleared ahead of the step (epochs restart at 1 in every launch: a region cleared once serves one)."""
         if not self.use_persistent:
             return None
         nbytes = int(self.lib._lvsr_bigru_persist_ws_bytes(int(B), int(H)))
@@ -193,14 +226,27 @@ class Encoder(object):
             return None
         if self.persist_auto and int(self.lib._lvsr_bigru_persist_rows(int(B), int(H))) > self.PERSIST_MAX_ROWS:
             return None
-        return self.ws.get(self._n(i, "sync"), ((nbytes + 3) // 4,), torch.int32)
+        return self.ws.get(self._n(i, "sync_bwd" if bwd else "sync"), ((nbytes + 3) // 4,), torch.int32)
+
+    def _clear_planes(self, B):
+        """-> {layer: the BPTT launch's workspace} of the layers that run on the persistent kernels, after ONE launch that zeroes
+        both workspaces of each behind their first 256 bytes (the sticky abort word).  Nothing else touches them until their launch."""
+        own, ranges = {}, []
+        for i, H in enumerate(self.d.Hs):
+            fwd = self._sync_ws(i, B, H)
+            if fwd is not None:
+                own[i] = self._sync_ws(i, B, H, bwd=True)
+                ranges += [(t.data_ptr() + 256, t.numel() * 4 - 256) for t in (fwd, own[i])]
+        if ranges:
+            self.lib.clear_many(ranges, own[min(own)])
+        return own
 
     def check_persistent(self):
         """After a synchronisation point: raise if a persistent kernel gave up waiting for its cluster.  The abort word is sticky
         (no launch clears it: a forward cluster that gave up is still reported after the backward pass and after replayed steps, and
         every later launch on the workspace leaves at once); it is cleared here, when the failure has been reported."""
         for k, t in self.ws._bufs.items():
-            if k[0].startswith("enc") and k[0].endswith(".sync") and int(t[0]) != 0:
+            if k[0].startswith("enc") and k[0].endswith((".sync", ".sync_bwd")) and int(t[0]) != 0:
                 t[:64].zero_()
                 raise RuntimeError("persistent BiGRU kernel aborted (a work-group of the cluster was not scheduled); results since "
                                    "the last check are invalid")
@@ -318,6 +364,10 @@ class Encoder(object):
         m = None if mask is None else mask.contiguous()
         saved = []
         gemm_ws = ws.get("gemm_ws", (1 << 22,))
+        # a pass that saves for a backward pass (the training step) copies and clears for all its layers in front of the first;
+        # any other caller (analyze, generate, decoding) issues the per-layer launches it always did
+        msubs = self._layer_inputs(m, T, B) if save_for_backward else None
+        cleared = self._clear_planes(B) if self.preclear and save_for_backward else {}
         for i, (H, s) in enumerate(zip(d.Hs, d.subsample)):
             I = d.layer_input_dim(i)
             Ts = (T + s - 1) // s
@@ -331,7 +381,7 @@ class Encoder(object):
             x2, xg2 = x.view(T * B, I), xg.view(T * B, 6 * H)
             sync = self._sync_ws(i, B, H)
             pk = self._packed(i) if sync is None else None     # the persistent kernels read the plain weights
-            Wcat, bcat = self._fork_cat(i)
+            Wcat, bcat = (self._cats[i]["W"], self._cats[i]["b"]) if msubs is not None else self._fork_cat(i)
             lib.sgemm(x2, Wcat, xg2, bias=bcat)          # all input projections of the layer, both directions
             h0s = [p[self._names(i, direction)["h0"]] for direction in ("forward", "backward")]
             if sync is not None:      # persistent cluster kernel: reads the plain weights and shards them into LDS itself
@@ -342,13 +392,16 @@ class Encoder(object):
             # (a persistent layer is a memset + one launch: no graph to build, and no host wait for a time-loop graph to drain)
             lib.run("lvsr_bigru_fwd", "lvsr_bigru_fwd_args", y, self.use_graph and sync is None, xg=xg, mask=m, Whh_p=Whh, Whg_p=Whg, h0=h0s,
                     y=y, ysub=(ysub if s > 1 else None), u=u, r=r, c=c, rh=rh, sub=s, T=T, B=B, H=H,
-                    persistent=int(sync is not None), sync_ws=sync)
-            saved.append(dict(x=x, mask=m, T=T, y=y, u=u, r=r, c=c, rh=rh))
+                    persistent=(0 if sync is None else 5 if i in cleared else 1), sync_ws=sync)
+            saved.append(dict(x=x, mask=m, T=T, y=y, u=u, r=r, c=c, rh=rh, sync_bwd=cleared.get(i)))
             x = ysub
             if m is not None and s > 1:
-                mm = ws.get(self._n(i, "msub"), (Ts, B))
-                mm.copy_(m[::s])
-                m = mm
+                if msubs is not None:
+                    m = msubs[i]
+                else:
+                    mm = ws.get(self._n(i, "msub"), (Ts, B))
+                    mm.copy_(m[::s])
+                    m = mm
             T = Ts
         if m is None:
             m = ws.get(self.pfx + ".ones_mask", (T, B))
@@ -368,6 +421,7 @@ class Encoder(object):
         assert self._saved is not None, "apply() must run first"
         gemm_ws = ws.get("gemm_ws", (1 << 22,))
         self._scatter = []
+        h0_sums = []          # (dh, Bp, H, dh0 forward, dh0 backward) of the persistent layers: summed in one launch behind the loop
         dy = d_encoded.contiguous()
         B = int(dy.shape[1])
         for i in reversed(range(d.n_layers)):
@@ -379,6 +433,10 @@ class Encoder(object):
             dh_ws = ws.get(self._n(i, "dh"), (12 * Bp * H,))
             nf, nb = self._names(i, "forward"), self._names(i, "backward")
             sync = self._sync_ws(i, B, H)
+            # planes the forward pass cleared for this launch: good for ONE launch (a second backward() clears its own)
+            own = sv.pop("sync_bwd", None) if sync is not None else None
+            if own is not None:
+                sync = own
             pk = self._packed(i) if sync is None else None
             if sync is not None:
                 WhhT, WhgT = [p[nf["Whh"]], p[nb["Whh"]]], [p[nf["Whg"]], p[nb["Whg"]]]
@@ -387,7 +445,9 @@ class Encoder(object):
             lib.run("lvsr_bigru_bwd", "lvsr_bigru_bwd_args", dxg, self.use_graph and sync is None, mask=sv["mask"], y=sv["y"],
                     u=sv["u"], r=sv["r"], c=sv["c"], WhhT_p=WhhT, WhgT_p=WhgT, h0=[p[nf["h0"]], p[nb["h0"]]], dy=dy,
                     dxg=dxg, dh_ws=dh_ws, dh0=[g[nf["h0"]], g[nb["h0"]]], sub=s, T=T, B=B, H=H,
-                    persistent=int(sync is not None), sync_ws=sync)
+                    persistent=(0 if sync is None else 7 if own is not None else 3), sync_ws=sync)
+            if sync is not None:      # (every layer has a dh workspace of its own: nothing overwrites it before the sum)
+                h0_sums.append((dh_ws, Bp, H, g[nf["h0"]], g[nb["h0"]]))
             x2 = sv["x"].view(T * B, I)
             dxg2 = dxg.view(T * B, 6 * H)
             y2 = sv["y"].view(T * B, 2 * H)
@@ -440,13 +500,18 @@ class Encoder(object):
                     # decoder's) run NOW on the side stream, beside the next layer's recurrence, not in one launch at the end
                     group.flush(ws.get("gemm_ws.grouped.side", (1 << 26,)))
             dy = dx
+        if h0_sums:
+            arr = (lib.structs["lvsr_h0_desc"] * len(h0_sums))()
+            for e, (dh, Bp, H, out_f, out_b) in zip(arr, h0_sums):
+                e.dh, e.out_f, e.out_b, e.Bp, e.B, e.H = dh.data_ptr(), out_f.data_ptr(), out_b.data_ptr(), Bp, B, H
+            lib.call("lvsr_bigru_h0_many", lib.stream_for(h0_sums[0][0]), arr, len(h0_sums))
         self.join_side_stream()
         if group is None:      # nothing was deferred: the fork gradients are there
             self.finish_backward()
         return dy
 
     def finish_backward(self):
-        """Scatter the concatenated fork gradients of all layers into the four parameters each (one launch per 32 pieces).
+        """Scatter the concatenated fork gradients of all layers into the four parameters each (one launch per 64 pieces).
         backward(group=...) leaves this to its caller: it must follow the group's flush, which runs the fork column sums."""
         self.lib.copy_many(self._scatter)
         self._scatter = []

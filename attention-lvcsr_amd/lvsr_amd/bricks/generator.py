@@ -220,7 +220,7 @@ class SequenceGenerator(object):
         f.update(self._gru_fields(pk), Ws_p=pk["Ws"])
         return f
 
-    def _feedback_forks(self, labels_flat, nrows, layers, fb_buf=None):
+    def _feedback_forks(self, labels_flat, nrows, layers, fb_buf=None, pair=False):
         """xg (nrows,3D) = fork(feedback(labels)) for every (parameter names, xg) of `layers`: LookupFeedback / OneOfNFeedback
         then Fork of two Linear bricks (sequence_generators.py:263-264, 839-842; lvsr/bricks/__init__.py:97-104); one pair
         here, one per layer of a stack (fork_inputs#l)."""
@@ -233,13 +233,17 @@ class SequenceGenerator(object):
             if d.embed:
                 lib.sgemm(fb_buf, p[n["Wfi"]], xg[:, : d.D], bias=p[n["bfi"]])
                 lib.sgemm(fb_buf, p[n["Wfg"]], xg[:, d.D:], bias=p[n["bfg"]])
+            elif pair:        # (the training step) both fork matrices by the one label list: one launch
+                lib.call("lvsr_gather_rows_pair", st, ptr(labels_flat), nrows, d.FB,
+                         ptr(p[n["Wfi"]]), d.D, d.D, ptr(p[n["bfi"]]), ptr(xg), 3 * d.D,
+                         ptr(p[n["Wfg"]]), 2 * d.D, 2 * d.D, ptr(p[n["bfg"]]), ptr(xg[:, d.D:]), 3 * d.D)
             else:
                 lib.call("lvsr_gather_rows", st, ptr(p[n["Wfi"]]), d.D, ptr(labels_flat), nrows, d.FB, d.D,
                          ptr(p[n["bfi"]]), ptr(xg), 3 * d.D)
                 lib.call("lvsr_gather_rows", st, ptr(p[n["Wfg"]]), 2 * d.D, ptr(labels_flat), nrows, d.FB, 2 * d.D,
                          ptr(p[n["bfg"]]), ptr(xg[:, d.D:]), 3 * d.D)
 
-    def _feedback_forks_backward(self, l, n, sv, DXG, dfb, wgrad):
+    def _feedback_forks_backward(self, l, n, sv, DXG, dfb, wgrad, pair=False):
         """Layer l's share of the backward pass of `_feedback_forks` (n = its parameter names, DXG (rows,3D) the gradient of its
         xg): the fork's weight gradients; with lookup feedback the gradient of the embedded labels `dfb` adds up over the layers
         and goes to the table after the last."""
@@ -254,6 +258,10 @@ class SequenceGenerator(object):
             if l == d.n_dec - 1:
                 lib.call("lvsr_scatter_add_rows", st, ptr(dfb), d.FB, ptr(labels_flat), nrows, d.V + 1, d.FB,
                          ptr(g[self.n["table"]]), d.FB, 0.0)
+        elif pair:
+            lib.call("lvsr_scatter_add_rows_pair", st, ptr(labels_flat), nrows, d.FB,
+                     ptr(dpc), 3 * d.D, d.D, ptr(g[n["Wfi"]]), d.D, 0.0,
+                     ptr(dg), 3 * d.D, 2 * d.D, ptr(g[n["Wfg"]]), 2 * d.D, 0.0)
         else:
             lib.call("lvsr_scatter_add_rows", st, ptr(dpc), 3 * d.D, ptr(labels_flat), nrows, d.FB, d.D,
                      ptr(g[n["Wfi"]]), d.D, 0.0)
@@ -382,6 +390,9 @@ class SequenceGenerator(object):
         L, B = int(outputs.shape[0]), int(outputs.shape[1])
         Tp = int(attended.shape[0])
         pk = self._packed(packs=False)
+        # a pass that saves for a backward pass (the training step) shares launches between neighbours (`_forward_recurrent`); any
+        # other caller (analyze) issues the launches it always did
+        self._merge_launches = bool(save_for_backward)
         A = attended.contiguous()
         Am = attended_mask.contiguous()
         labels = outputs.contiguous()
@@ -430,13 +441,11 @@ class SequenceGenerator(object):
         d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
         xg = ws.get("gen.xg", (L * B, 3 * d.D))
         fb = ws.get("gen.fb", (L * B, d.FB)) if d.embed else None
-        self._feedback_forks(labels.view(-1), L * B, [(n, xg)], fb)
+        merge = getattr(self, "_merge_launches", False)
+        self._feedback_forks(labels.view(-1), L * B, [(n, xg)], fb, pair=merge)
         bufs = self._attdec_bufs("gen.", "", L, B, Tp, ZB=True, xg=xg, ymask=ym)
         S, W = bufs["S"], bufs["W"]
-        S[0].copy_(p[n["h0"]].unsqueeze(0).expand(B, d.D))     # initial_state tiled (recurrent.py:622-624)
-        W[0].zero_()
-        if d.conv:
-            W[0, :, 0] = 1.0                                   # initial_glimpses (lvsr/bricks/attention.py:215-222)
+        self._initial_slots(S, W, B, Tp, merge)
         fields = self._attdec_fields(pk, A, PA, Am, L, B, bufs, phases=3, step0=0, broadcast=False)
         sync = self._persistent_ws(fields)
         if sync is not None:
@@ -453,6 +462,28 @@ class SequenceGenerator(object):
             self._ensure_packs(pk)
             fwd_args = lib.run("lvsr_attdec_fwd", "lvsr_attdec_args", S, self.use_graph, **fields)
         return dict(bufs=bufs, saved=dict(xg=xg, fb=fb, fields=fields, AW_valid=sync is not None))
+
+    def _initial_slots(self, S, W, B, Tp, merge):
+        """Slot 0 of the teacher-forced pass: S[0] = initial_state tiled (recurrent.py:622-624), W[0] = initial_glimpses (one-hot on
+        frame 0 with a location-aware attention, else zeros; lvsr/bricks/attention.py:215-222) — two row broadcasts in ONE launch (a
+        copy, a fill and a strided fill before).  The row W[0] repeats lives in a workspace of its own, written when it comes into
+        being; without `merge`, and inside a graph capture that finds the row new (a captured write would never run if the capture
+        is dropped), the three plain operations are enqueued."""
+        d, p, n, lib, ws = self.d, self.store.p, self.n, self.lib, self.ws
+        row = ws.get("gen.W0_row", (Tp,)) if merge else None
+        if row is None or getattr(self, "_w0_row_ptr", None) != row.data_ptr():
+            if row is None or lib.capturing:
+                S[0].copy_(p[n["h0"]].unsqueeze(0).expand(B, d.D))
+                W[0].zero_()
+                if d.conv:
+                    W[0, :, 0] = 1.0
+                return
+            base = ws._bufs[("gen.W0_row", torch.float32)]
+            base.zero_()
+            if d.conv:
+                base[0] = 1.0
+            self._w0_row_ptr = row.data_ptr()
+        lib.copy_many([(p[n["h0"]].unsqueeze(0).expand(B, d.D), S[0]), (row.unsqueeze(0).expand(B, Tp), W[0])])
 
     def _lm_lookahead(self, lm, labels, ym, L, B):
         """(L*B, V) look-ahead costs `lm_add` of the teacher-forced label sequences: row (i, b) = FSTCostsOp of the state set after
@@ -573,8 +604,9 @@ class SequenceGenerator(object):
         DWA = dWA_r.view(L, B, d.E)
         DSW = ws.get("gen.DSW", (nrows, d.M))
         DCV = ws.get("gen.DCV", (L, B, Kc, Tp)) if d.conv else None
-        dPA = ws.get("gen.dPA", (Tp, B, d.M), zero=True)
-        ds = ws.get("gen.ds", (B, d.D), zero=True)
+        dPA = ws.get("gen.dPA", (Tp, B, d.M))
+        ds = ws.get("gen.ds", (B, d.D))
+        lib.clear_many([(dPA.data_ptr(), dPA.numel() * 4), (ds.data_ptr(), ds.numel() * 4)], ds)       # both accumulate: one launch
         wd = ws.get("gen.Wd_cat", (d.E, 3 * d.D))
         AW, AW_ld = self._AW(Tp, B)
         if not sv.get("AW_valid"):
@@ -615,7 +647,7 @@ class SequenceGenerator(object):
         colsum(ds, g[n["h0"]])
         colsum(dpc, g[n["bfi"]])
         colsum(dg, g[n["bfg"]])
-        self._feedback_forks_backward(0, n, sv, DXG, ws.get("gen.dfb", (nrows, d.FB)) if d.embed else None, wgrad)
+        self._feedback_forks_backward(0, n, sv, DXG, ws.get("gen.dfb", (nrows, d.FB)) if d.embed else None, wgrad, pair=True)
         return dict(accH=accH, accWe=accWe, accEb=accEb, DCV=DCV, dPA=dPA, DWA=DWA, fwd_args=fwd_args)
 
     # ---- generation mode (what BeamSearch drives: libs/blocks/blocks/search.py:97-142) -----------------------

@@ -251,7 +251,7 @@ class Lib(object):
 
     def copy_many(self, pairs):
         """pairs: [(src, dst)] or [(src, dst, beta)] of equally shaped 1-D / 2-D fp32 tensors with unit inner stride -> one
-        lvsr_copy2d_many launch (per 32 pairs); beta != 0: dst = src + beta * dst."""
+        lvsr_copy2d_many launch (per 64 pairs); beta != 0: dst = src + beta * dst."""
         if not pairs:
             return
         cls = self.structs["lvsr_copy_desc"]
@@ -265,6 +265,15 @@ class Lib(object):
             d.lds = src.stride(0) if src.dim() == 2 else cols
             d.ldd = dst.stride(0) if dst.dim() == 2 else cols
         self.call("lvsr_copy2d_many", self.stream_for(pairs[0][1]), arr, len(pairs))
+
+    def clear_many(self, ranges, ref):
+        """ranges: [(address, bytes)] -> zeroed by one lvsr_clear_many launch (per 64) on the stream of tensor `ref`."""
+        if not ranges:
+            return
+        arr = (self.structs["lvsr_clear_desc"] * len(ranges))()
+        for d, (address, nbytes) in zip(arr, ranges):
+            d.ptr, d.bytes = int(address), int(nbytes)
+        self.call("lvsr_clear_many", self.stream_for(ref), arr, len(ranges))
 
     def transpose(self, x, out):
         self.call("lvsr_transpose", self.stream_for(out), ptr(x), x.shape[0], x.shape[1], ptr(out))

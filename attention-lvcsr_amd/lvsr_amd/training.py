@@ -26,7 +26,7 @@ logger = logging.getLogger(__name__)
 
 def _is_sync_word(key):
     """Workspace names of the cluster kernels' scratch (abort word first): decoder, encoder layers (and their passes)."""
-    return key[0] in ("gen.sync", "gen.sync_bwd") or (key[0].startswith("enc") and key[0].endswith(".sync"))
+    return key[0] in ("gen.sync", "gen.sync_bwd") or (key[0].startswith("enc") and key[0].endswith((".sync", ".sync_bwd")))
 
 
 class Trainer(object):

@@ -52,7 +52,8 @@ int lvsr_region_end(void* stream, int keep);
 #define LVSR_KNOB_GEMM_MID_TILES 6    /* lvsr_sgemm with K <= 2048 uses 64 x 64 tiles when the output has fewer 128 x 128 tiles than this (0 = 2048; 1 = never) */
 #define LVSR_KNOB_DEC_CLUSTER 7       /* persistent decoder at D <= 256: 0 = clusters of 16 work-groups per utterance when they fit the chip, else 8; 8 / 16 = only that */
 #define LVSR_KNOB_ENERGY_ROWS 8       /* step-kernel energies (row groups): rows of a group per work-group; 0 = 8 while the grid is at most one round of work-groups, else all */
-#define LVSR_KNOB_COUNT 9
+#define LVSR_KNOB_OPT_UNFUSED 9      /* lvsr_opt_step: 0 = the rules and max-norm kernels test their steps for RemoveNotFinite themselves; 1 = a pass of its own (opt_finite_kernel) does */
+#define LVSR_KNOB_COUNT 10
 int lvsr_set_knob(int knob, int value);
 int lvsr_get_knob(int knob);
 
@@ -80,7 +81,7 @@ int lvsr_sgemm_tn_grouped(void* stream, const lvsr_gemm_desc* descs, int n, floa
 /* How lvsr_sgemm_tn_grouped cuts the same member list given `ws_bytes` of workspace (<= 0: none): ksplit[i] k-chunks of kchunk[i]
  * rows for member i (the last one shorter).  A function of the members' M, N, K and ws_bytes only. */
 int lvsr_sgemm_tn_grouped_plan(const lvsr_gemm_desc* descs, int n, long long ws_bytes, int* ksplit, int* kchunk);
-/* n independent strided 2-D copies (dst[r*ldd + c] = src[r*lds + c]) in ONE launch per 32 descriptors: the concatenated
+/* n independent strided 2-D copies (dst[r*ldd + c] = src[r*lds + c]) in ONE launch per 64 descriptors: the concatenated
  * fork weights of the encoder layers ((I,6H) = [Wi_f | Wg_f | Wi_b | Wg_b], refreshed per step) and the scatter of their
  * gradient back into the four parameters were 8 copy kernels of ~5 us per layer and pass. */
 typedef struct lvsr_copy_desc {
@@ -89,6 +90,14 @@ typedef struct lvsr_copy_desc {
     float beta;                           /* dst = src + beta * dst (0: plain copy, dst is not read) */
 } lvsr_copy_desc;
 int lvsr_copy2d_many(void* stream, const lvsr_copy_desc* descs, int n);
+/* n byte ranges set to zero in ONE launch (per 64): any address, any byte count (16-byte stores between the first and the last
+ * 16-byte boundary of a range, single bytes at its ends).  Here: the granule planes of all persistent encoder launches of a training
+ * step, in front of the first of them (a memset node in front of each before). */
+typedef struct lvsr_clear_desc {
+    void* ptr;
+    long long bytes;
+} lvsr_clear_desc;
+int lvsr_clear_many(void* stream, const lvsr_clear_desc* descs, int n);
 /* out[n] = beta*out[n] + sum_m X[m*ldx+n]  (bias gradients); ws: optional workspace for the row-split partials */
 int lvsr_colsum(void* stream, const float* X, int M, int N, int ldx, float* out, float beta, float* ws,
                 long long ws_bytes);
@@ -132,7 +141,10 @@ typedef struct lvsr_bigru_fwd_args {
     int sub, T, B, H;
     int kernel_mask;        /* 0 or 3: both step kernels; 1 / 2: only the gates / candidate kernel (timing probes) */
     int persistent;         /* 1: one persistent launch for the whole time loop (needs sync_ws; Whh_p / Whg_p are then the
-                               PLAIN (H,H) / (H,2H) weights), 0: two kernels per step */
+                               PLAIN (H,H) / (H,2H) weights), 0: two kernels per step.  Bits on top of 1 (a field of their own would
+                               change the argument layout of the persistent kernels, which take this block by value):
+                               4 = everything in sync_ws behind its first 256 bytes is zero already and no other launch has used it
+                               since (lvsr_clear_many at the head of a step): the launch does not clear its planes itself */
     void* sync_ws;          /* lvsr_bigru_persist_ws_bytes(B,H) bytes of device scratch for the persistent mode */
 } lvsr_bigru_fwd_args;
 int lvsr_bigru_fwd(void* stream, const lvsr_bigru_fwd_args* a, int use_graph);
@@ -149,10 +161,18 @@ typedef struct lvsr_bigru_bwd_args {
     float* dh0[2];           /* (H) out: gradient wrt initial_state */
     int sub, T, B, H;
     int kernel_mask;         /* 0 or 3: both step kernels; 1 / 2: only kernel A / kernel B (timing probes) */
-    int persistent;          /* as in lvsr_bigru_fwd_args */
+    int persistent;          /* as in lvsr_bigru_fwd_args (bit 4 included); bit 2 = dh0 is left to the caller's lvsr_bigru_h0_many */
     void* sync_ws;
 } lvsr_bigru_bwd_args;
 int lvsr_bigru_bwd(void* stream, const lvsr_bigru_bwd_args* a, int use_graph);
+/* dh0 of n persistent lvsr_bigru_bwd calls made with bit 2 of `persistent`, in ONE launch (per 16) behind the last of them: out_f[j] /
+ * out_b[j] = sum over b (ascending) of the per-utterance initial-state gradients the call left in its dh_ws — what the call itself
+ * computes without the bit (one launch of ~5 us per layer).  dh = that call's dh_ws, Bp = B rounded up to 16. */
+typedef struct lvsr_h0_desc {
+    const float* dh; float* out_f; float* out_b;
+    int Bp, B, H, pad0;
+} lvsr_h0_desc;
+int lvsr_bigru_h0_many(void* stream, const lvsr_h0_desc* descs, int n);
 /* Persistent mode (csrc/encoder_persist.hip): a cluster of P = ceil(H/64)^2/4 work-groups (1 at H <= 128, 4 at H <= 256, 16 at
  * H <= 512; one per CU) serves `rows` utterances of one direction; every thread keeps 192 recurrent weights in registers
  * for the whole sequence and the cluster exchanges h / r*h (forward) or dpre_c, dpre_u / dpre_r (backward) once per phase
@@ -348,6 +368,15 @@ int lvsr_gather_rows(void* stream, const float* table, int ldt, const long long*
  * dst is not read).  Limit: nrows <= 65535 (one work-group row of the grid per destination row); more is refused.  n is not limited */
 int lvsr_scatter_add_rows(void* stream, const float* src, int lds, const long long* idx, int n, int nrows, int width,
                           float* dst, int ldd, float beta);
+/* lvsr_gather_rows / lvsr_scatter_add_rows twice by ONE index list, as one launch: (a) and (b) each as in the single form (a width of
+ * 0 leaves that half out) — the two fork matrices of a one-hot feedback (fork_inputs.W, fork_gate_inputs.W) and their gradients.  The
+ * outputs of (a) and (b) must not overlap; every output element is computed exactly as the single form computes it. */
+int lvsr_gather_rows_pair(void* stream, const long long* idx, int n, int nrows, const float* table_a, int ldt_a, int width_a,
+                          const float* bias_a, float* out_a, int ldo_a, const float* table_b, int ldt_b, int width_b,
+                          const float* bias_b, float* out_b, int ldo_b);
+int lvsr_scatter_add_rows_pair(void* stream, const long long* idx, int n, int nrows, const float* src_a, int lds_a, int width_a,
+                               float* dst_a, int ldd_a, float beta_a, const float* src_b, int lds_b, int width_b, float* dst_b,
+                               int ldd_b, float beta_b);
 /* kind: 0 identity, 1 Maxout(2), 2 Rectifier, 3 Tanh; x (n,P) -> y (n,P or P/2) */
 int lvsr_act_fwd(void* stream, int kind, const float* x, int ldx, int n, int P, float* y, int ldy);
 int lvsr_act_bwd(void* stream, int kind, const float* x, int ldx, const float* dy, int lddy, int n, int P, float* dx,
@@ -383,7 +412,9 @@ int lvsr_reward_mse(void* stream, int mode, const float* readouts, int ld, const
 /* ---- optimiser step on the flat buffers -----------------------------------------------------------
  * StepClipping -> Momentum(scale) -> AdaDelta -> Restrict(VariableClipping(axis=0), WEIGHT params) ->
  * RemoveNotFinite -> [BurnIn] -> parameter -= step  (lvsr/main.py:480-519; libs/blocks/blocks/algorithms/__init__.py:
- * 378-515, 610-720, 829-893).  `grad` holds d(sum cost); grad_scale = 1/batch_size (lvsr/main.py:340-345). */
+ * 378-515, 610-720, 829-893).  `grad` holds d(sum cost); grad_scale = 1/batch_size (lvsr/main.py:340-345).
+ * segflag[s] is raised by the kernels that make the steps, for every step of segment s that is not finite (LVSR_KNOB_OPT_UNFUSED = 1:
+ * by a pass of its own over `step`, which tests partial sums — finite steps whose sum overflows show there only). */
 typedef struct lvsr_opt_args {
     float* param; const float* grad;      /* flat (n) */
     float* velocity; float* ms_step; float* ms_dx;   /* flat (n) rule state (NULL when the rule is off) */
