@@ -455,6 +455,24 @@ __global__ __launch_bounds__(64 * FBF_WAVES) void fbank_fft_kernel(const short* 
 // clamp(t + k, first, last frame of t's utterance), which the clamp keeps inside the staged span.
 #define DC_TILE 56
 #define DC_MAXDIM 64
+// The element arithmetic both batched kernels share (deltas_cmvn_batch_kernel, frontend_batch_kernel), so that a frame has the same
+// bits whichever of them writes it: v9 = the static coefficient of frames t - 4 .. t + 4 (clamped to the utterance); the taps are
+// added from k = -2 (-4) upwards onto 0, each product fused into its addition.  The fused multiply-adds are spelled out: written as
+// `d += s * v` the contraction is the optimiser's choice per kernel (deltas_cmvn_batch_kernel got nine v_fma, frontend_batch_kernel
+// packed multiplies and separate additions: other bits); fmaf is what deltas_cmvn_batch_kernel always compiled to
+__device__ __forceinline__ void dc_deltas(const float (&v9)[9], float& d1, float& d2) {
+    const float s1[5] = {-0.2f, -0.1f, 0.f, 0.1f, 0.2f};
+    const float s2[9] = {0.04f, 0.04f, 0.01f, -0.04f, -0.1f, -0.04f, 0.01f, 0.04f, 0.04f};
+    d1 = 0.f;
+    d2 = 0.f;
+#pragma unroll
+    for (int k = -2; k <= 2; ++k) d1 = fmaf(s1[k + 2], v9[k + 4], d1);
+#pragma unroll
+    for (int k = -4; k <= 4; ++k) d2 = fmaf(s2[k + 4], v9[k + 4], d2);
+}
+// global CMVN of one value; without statistics the callers pass mean 0 and istd 1, which change no bit
+__device__ __forceinline__ float dc_normalise(float v, float mean, float istd) { return (v - mean) * istd; }
+
 __global__ __launch_bounds__(256) void deltas_cmvn_batch_kernel(const float* feats, const int* frame_off, int n_utts, int total_frames, int dim,
                                                                const float* mean, const float* istd, float* out) {
     __shared__ float rows[(DC_TILE + 8) * DC_MAXDIM];
@@ -495,8 +513,6 @@ __global__ __launch_bounds__(256) void deltas_cmvn_batch_kernel(const float* fea
             hi_of[threadIdx.x] = foff[u + 1] - 1;
         }
         __syncthreads();
-        const float s1[5] = {-0.2f, -0.1f, 0.f, 0.1f, 0.2f};
-        const float s2[9] = {0.04f, 0.04f, 0.01f, -0.04f, -0.1f, -0.04f, 0.01f, 0.04f, 0.04f};
         // thread = (frame slot, coefficient): the divisions by the run-time `dim` happen once per tile, not once per element (the
         // kernel is bound by vector-ALU issue: 152 vector instructions per wave and element before, profiles/r05_pmc_fbank.md)
         const int fpi = 256 / dim;                         // frames per iteration of the work-group (6 at dim = 41)
@@ -512,17 +528,106 @@ __global__ __launch_bounds__(256) void deltas_cmvn_batch_kernel(const float* fea
                 float v9[9];
 #pragma unroll
                 for (int k = -4; k <= 4; ++k) v9[k + 4] = rows[(min(t1, max(t0, t + k)) - ra) * dim + j];
-                float d1 = 0.f, d2 = 0.f;
-#pragma unroll
-                for (int k = -2; k <= 2; ++k) d1 += s1[k + 2] * v9[k + 4];
-#pragma unroll
-                for (int k = -4; k <= 4; ++k) d2 += s2[k + 4] * v9[k + 4];
+                float d1, d2;
+                dc_deltas(v9, d1, d2);
                 float* o = out + (size_t)t * 3 * dim + j;
-                o[0] = (v9[4] - mj[0]) * ij[0];
-                o[dim] = (d1 - mj[1]) * ij[1];
-                o[2 * dim] = (d2 - mj[2]) * ij[2];
+                o[0] = dc_normalise(v9[4], mj[0], ij[0]);
+                o[dim] = dc_normalise(d1, mj[1], ij[1]);
+                o[2 * dim] = dc_normalise(d2, mj[2], ij[2]);
             }
     }
+}
+
+// The recognizer's input batch straight from the packed static features: x (T, n, W) time-major and mask (T, n), W = 3 dim with
+// deltas and dim without.  A work-group owns DC_TILE consecutive frames of ONE utterance (grid = tiles of T x utterances: it depends
+// on the sizes alone): the utterance's rows [tile - 4, tile + DC_TILE + 4) are one contiguous span of `feats`, staged in LDS as above;
+// a frame's neighbours are clamped to its own utterance, so nothing of the neighbouring utterances is read.  Thread = (frame slot,
+// output column w): the lanes of a wave write consecutive floats of an output row — 4 W contiguous bytes, the next frame's row
+// n W floats further on — and a thread keeps the one of static | delta | delta-delta (dc_deltas) its column holds.  Frames at and behind the utterance's end are written as +0.0f with mask 0 by the same threads: no memset in front.
+// The kernel stays inside its buffers whatever `frame_off` holds: an utterance is cut at T, offsets outside [0, total_frames] or
+// out of order give an empty column.
+__global__ __launch_bounds__(256) void frontend_batch_kernel(const float* feats, const int* frame_off, int total_frames, int dim, int with_deltas,
+                                                            const float* mean, const float* istd, int T, int n_utts, float* x, float* mask) {
+    __shared__ float rows[(DC_TILE + 8) * DC_MAXDIM];
+    const int b = blockIdx.y;
+    const int ta = blockIdx.x * DC_TILE, tb = min(T, ta + DC_TILE);                   // frames [ta, tb) of column b
+    const int f0 = frame_off[b], f1 = frame_off[b + 1];
+    const int len = (f0 < 0 || f1 < f0 || f1 > total_frames) ? 0 : min(f1 - f0, T);   // frames of this utterance that are written
+    const int ra = max(0, ta - 4), rb = min(len, tb + 4);                             // staged rows [ra, rb) of the utterance
+    if (rb > ra) {
+        const float* src = feats + (size_t)(f0 + ra) * dim;
+        const int cnt = (rb - ra) * dim;
+        for (int i = threadIdx.x; i < cnt; i += 256) rows[i] = src[i];
+    }
+    __syncthreads();
+    const int W = with_deltas ? 3 * dim : dim;
+    const int fpi = 256 / W;                                // frames per iteration of the work-group (2 at W = 123)
+    const int tl0 = threadIdx.x / W, w = threadIdx.x - tl0 * W;
+    if (tl0 >= fpi) return;
+    const int q = w / dim, j = w - q * dim;                 // q: 0 static, 1 delta, 2 delta-delta
+    const float mw = mean ? mean[w] : 0.f, iw = mean ? istd[w] : 1.f;
+    for (int t = ta + tl0; t < tb; t += fpi) {
+        float r = 0.f;
+        if (t < len) {
+            float v9[9];
+#pragma unroll
+            for (int k = -4; k <= 4; ++k) v9[k + 4] = rows[(min(len - 1, max(0, t + k)) - ra) * dim + j];
+            float d1, d2;
+            dc_deltas(v9, d1, d2);
+            r = dc_normalise(q == 0 ? v9[4] : (q == 1 ? d1 : d2), mw, iw);
+        }
+        x[((size_t)t * n_utts + b) * W + w] = r;
+        if (w == 0) mask[(size_t)t * n_utts + b] = t < len ? 1.f : 0.f;
+    }
+}
+
+// Per-column sums of x and x^2 for global CMVN (the reference's Normalization, lvsr/preprocessing.py:13-35), in float64: x (rows,
+// width) contiguous.  Stage 1: work-group p takes the rows [p R, (p + 1) R), R = ceil(rows / parts); thread = (row slot, column), the
+// row slots striding over the part's rows, each thread adding its values and their float64 squares (exact products) in row order; the
+// row slots of a column are then added in slot order through LDS.  Stage 2 adds the parts of every sum (64 strided runs, then a tree).
+// Every order depends on (rows, width) alone: no atomics, two runs give the same bits.
+#define FS_MAXW 256
+#define FS_MAX_PARTS 1024
+#define FS_PART_ROWS 64          // rows of a part at the least
+__global__ __launch_bounds__(256) void feature_stats_part_kernel(const float* x, long long rows, int width, long long part_rows, double* partials) {
+    __shared__ double red[2][256];
+    const int fpi = 256 / width;
+    const int s0 = threadIdx.x / width, j = threadIdx.x - s0 * width;
+    const long long r0 = (long long)blockIdx.x * part_rows, r1 = min(rows, r0 + part_rows);
+    double s = 0.0, s2 = 0.0;
+    if (s0 < fpi)
+        for (long long r = r0 + s0; r < r1; r += fpi) {
+            const double v = (double)x[(size_t)r * width + j];
+            s += v;
+            s2 += v * v;
+        }
+    red[0][threadIdx.x] = s;
+    red[1][threadIdx.x] = s2;
+    __syncthreads();
+    if (s0 == 0) {
+        for (int k = 1; k < fpi; ++k) { s += red[0][k * width + j]; s2 += red[1][k * width + j]; }
+        double* o = partials + (size_t)blockIdx.x * 2 * width;
+        o[j] = s;
+        o[width + j] = s2;
+    }
+}
+// stage 2: a work-group takes FS_SUM_COLS of the (2 width) sums; thread = (part slot, column): the 64 slots stride over the parts in
+// order (lanes along the columns: contiguous doubles of a part), then a fixed tree over the slots in LDS
+#define FS_SUM_COLS 4
+__global__ __launch_bounds__(256) void feature_stats_sum_kernel(const double* partials, int parts, int width, double* sums, int accumulate) {
+    __shared__ double red[64][FS_SUM_COLS];
+    const int slot = threadIdx.x / FS_SUM_COLS, cl = threadIdx.x % FS_SUM_COLS;
+    const int c = blockIdx.x * FS_SUM_COLS + cl;           // column of the (2 width) sums
+    double s = 0.0;
+    if (c < 2 * width)
+        for (int p = slot; p < parts; p += 64) s += partials[(size_t)p * 2 * width + c];
+    red[slot][cl] = s;
+    __syncthreads();
+    for (int half = 32; half > 0; half >>= 1) {
+        if (slot < half) red[slot][cl] += red[slot + half][cl];
+        __syncthreads();
+    }
+    if (slot == 0 && c < 2 * width) sums[c] = accumulate ? sums[c] + red[0][cl] : red[0][cl];
 }
 
 extern "C" {
@@ -583,6 +688,35 @@ int lvsr_add_deltas_cmvn_batch(void* stream, const float* feats, const int* fram
     const int nb = ntiles > 8192 ? 8192 : ntiles;
     hipLaunchKernelGGL(deltas_cmvn_batch_kernel, dim3(nb), dim3(256), 0, (hipStream_t)stream, feats, frame_off, n, total_frames, dim, mean, istd, out);
     return lvsr_check_launch("lvsr_add_deltas_cmvn_batch");
+}
+
+int lvsr_frontend_batch(void* stream, const float* feats, const int* frame_off, int n, int total_frames, int max_frames, int dim,
+                        int with_deltas, const float* mean, const float* istd, int T, float* x, float* mask) {
+    LVSR_REQUIRE(frame_off && x && mask && n > 0 && dim > 0 && total_frames >= 0 && (feats || total_frames == 0), "lvsr_frontend_batch: bad arguments");
+    LVSR_REQUIRE(dim <= DC_MAXDIM, "lvsr_frontend_batch: at most %d coefficients per frame (dim = %d)", DC_MAXDIM, dim);
+    LVSR_REQUIRE((mean == nullptr) == (istd == nullptr), "lvsr_frontend_batch: mean and istd come together or not at all");
+    LVSR_REQUIRE(n <= 65535, "lvsr_frontend_batch: at most 65535 utterances per launch (n = %d)", n);
+    LVSR_REQUIRE(max_frames >= 0 && max_frames <= total_frames && (long long)max_frames * n >= total_frames,
+                 "lvsr_frontend_batch: max_frames = %d is not the longest of %d utterances with %d frames in all", max_frames, n, total_frames);
+    LVSR_REQUIRE(T > 0 && T >= max_frames, "lvsr_frontend_batch: T = %d is shorter than the longest utterance (%d frames)", T, max_frames);
+    hipLaunchKernelGGL(frontend_batch_kernel, dim3((T + DC_TILE - 1) / DC_TILE, n), dim3(256), 0, (hipStream_t)stream, feats, frame_off, total_frames,
+                       dim, with_deltas ? 1 : 0, mean, istd, T, n, x, mask);
+    return lvsr_check_launch("lvsr_frontend_batch");
+}
+
+int lvsr_feature_stats(void* stream, const float* x, long long rows, int width, double* partials, double* sums, int accumulate) {
+    LVSR_REQUIRE(partials && sums && rows >= 0 && (x || rows == 0), "lvsr_feature_stats: bad arguments");
+    LVSR_REQUIRE(width > 0 && width <= FS_MAXW, "lvsr_feature_stats: at most %d columns (width = %d)", FS_MAXW, width);
+    long long parts = (rows + FS_PART_ROWS - 1) / FS_PART_ROWS;
+    if (parts > FS_MAX_PARTS) parts = FS_MAX_PARTS;
+    hipStream_t s = (hipStream_t)stream;
+    if (parts > 0) {
+        const long long part_rows = (rows + parts - 1) / parts;
+        hipLaunchKernelGGL(feature_stats_part_kernel, dim3((unsigned)parts), dim3(256), 0, s, x, rows, width, part_rows, partials);
+    }
+    hipLaunchKernelGGL(feature_stats_sum_kernel, dim3((2 * width + FS_SUM_COLS - 1) / FS_SUM_COLS), dim3(256), 0, s, (const double*)partials, (int)parts, width, sums,
+                       accumulate);
+    return lvsr_check_launch("lvsr_feature_stats");
 }
 
 }  // extern "C"

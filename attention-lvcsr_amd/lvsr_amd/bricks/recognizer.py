@@ -474,6 +474,34 @@ class SpeechRecognizer(object):
         results = self._beam_search.search_batch(recs, self.eos_label, limits, ignore_first_eol=self.data_prepend_eos, **kwargs)
         return [r if isinstance(r, Exception) else ([[int(t) for t in o] for o in r[0]], [float(c) for c in r[1]]) for r in results]
 
+    def compute_contexts_staged(self, x, mask):
+        """The encoder pass of `compute_contexts_batch` over a batch that is already on the device (`frontend.FrontEnd.batch`):
+        x (T,B,F) float32, mask (T,B) float32 — or None: no input mask, as `compute_contexts` runs a single utterance.  No copy: the
+        tensors are read where they are, so they must keep their values until the searches that use the contexts have begun."""
+        tensors = [("x", x, 3)] + ([("mask", mask, 2)] if mask is not None else [])
+        for name, t, nd in tensors:
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != nd or not t.is_contiguous():
+                raise ValueError("compute_contexts_staged: %s must be a contiguous float32 tensor of %d dimensions" % (name, nd))
+            if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
+                raise ValueError("compute_contexts_staged: %s lives on %s, the recognizer on %s" % (name, t.device, self.device))
+        if int(x.shape[2]) != self.d.F:
+            raise ValueError("compute_contexts_staged: %d features per frame, the recognizer takes %d" % (x.shape[2], self.d.F))
+        if mask is not None and tuple(mask.shape) != tuple(x.shape[:2]):
+            raise ValueError("compute_contexts_staged: mask %s for recordings %s" % (tuple(mask.shape), tuple(x.shape)))
+        encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, False), mask, save_for_backward=False)
+        self.generator.init_generation(encoded, encoded_mask)
+
+    def beam_search_staged(self, x, mask, lengths, **kwargs):
+        """`beam_search_batch` for a batch staged on the device: x (T,B,F), mask (T,B), `lengths` the frames of every utterance (a
+        host sequence: the length limits are int(lengths[i] / max_decoded_length_scale), as for host recordings).  -> the same list of
+        (outputs, costs) or exceptions.  A host-side language model or a validator is refused (BeamSearch.search_staged)."""
+        self.init_beam_search(self.beam_size)
+        lengths = [int(n) for n in lengths]
+        limits = [int(n / self.max_decoded_length_scale) for n in lengths]
+        results = self._beam_search.search_staged(x, mask, limits, self.eos_label, lengths=lengths, ignore_first_eol=self.data_prepend_eos,
+                                                  **kwargs)
+        return [r if isinstance(r, Exception) else ([[int(t) for t in o] for o in r[0]], [float(c) for c in r[1]]) for r in results]
+
     def init_beam_search(self, beam_size):
         from ..search import BeamSearch
         if getattr(self, "_beam_search", None) is not None and self.beam_size == beam_size:

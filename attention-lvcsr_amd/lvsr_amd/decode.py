@@ -136,3 +136,51 @@ def search(recognizer, utterances, beam_size=10, char_discount=0.0, round_to_inf
     if to_words is not None:
         out["wer"] = tot_werr / float(max(1, tot_wlen))
     return out
+
+
+def recognize_plan(num_samples, batch, sort=True):
+    """The chunks `recognize` decodes: lists of indices into `num_samples` (the utterances' sample counts).  sort=True: in order of
+    decreasing length (equal lengths in input order), cut into chunks of `batch` — the utterances of a chunk are padded to its
+    longest, so chunks of like lengths mean less padding and fewer distinct graph shapes; sort=False: input order."""
+    batch = max(1, int(batch))
+    order = list(range(len(num_samples)))
+    if sort:
+        order.sort(key=lambda i: (-int(num_samples[i]), i))
+    return [order[i: i + batch] for i in range(0, len(order), batch)]
+
+
+def recognize(recognizer, front_end, waveforms, beam_size=10, batch=64, char_discount=0.0, round_to_inf=1e9, stop_on="patience",
+              to_text=None, sort=True):
+    """From waveforms to hypotheses: `waveforms` is a sequence of 1-D int16 arrays or of (id, array) pairs (ids default to the
+    position); `front_end` a `frontend.FrontEnd`.  Each chunk of `recognize_plan` goes through FrontEnd.batch (two launches; the PCM
+    is all that is copied to the device) and SpeechRecognizer.beam_search_staged.  -> one row per utterance IN INPUT ORDER:
+    dict(id=, recognized=, search_cost=, num_frames=) and text= when `to_text(labels)` is given; an utterance whose search finds no
+    candidate has recognized=[], search_cost=nan and error="CandidateNotFoundError", as in `search`."""
+    items = []
+    for number, w in enumerate(waveforms):
+        ident, samples = w if isinstance(w, tuple) else (number, w)
+        items.append((ident, samples))
+    if front_end.num_features != recognizer.d.F:
+        raise ValueError("recognize: the front end makes %d features per frame, the recognizer takes %d" % (front_end.num_features, recognizer.d.F))
+    num_samples = [int(len(s)) for _, s in items]
+    frames = [front_end.num_frames(n) for n in num_samples]
+    for (ident, _), n, f in zip(items, num_samples, frames):
+        if f <= 0:
+            raise ValueError("recognize: utterance %r has %d samples, fewer than one frame (%d samples)" % (ident, n, front_end.fbank.frame_length))
+    recognizer.init_beam_search(beam_size)
+    kw = dict(char_discount=char_discount, round_to_inf=round_to_inf, stop_on=stop_on)
+    rows = [None] * len(items)
+    for chunk in recognize_plan(num_samples, batch, sort):
+        x, mask, lengths = front_end.batch([items[i][1] for i in chunk])
+        for i, n, result in zip(chunk, lengths, recognizer.beam_search_staged(x, mask, lengths, **kw)):
+            row = dict(id=items[i][0], num_frames=int(n))
+            if isinstance(result, CandidateNotFoundError):
+                row.update(recognized=[], search_cost=float("nan"), error="CandidateNotFoundError")
+            elif isinstance(result, Exception):
+                raise result
+            else:
+                row.update(recognized=result[0][0], search_cost=result[1][0])
+            if to_text is not None:
+                row["text"] = to_text(row["recognized"])
+            rows[i] = row
+    return rows

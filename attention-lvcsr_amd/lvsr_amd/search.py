@@ -122,6 +122,36 @@ class BeamSearch(object):
         return self._begin(lambda: self.rec.compute_contexts_batch(recordings), max_lengths, eol_symbol, ignore_first_eol,
                            char_discount, round_to_inf, stop_on, False)
 
+    def _refuse_host_work(self, validate_solution_function, where):
+        lm = self.rec.generator.language_model
+        if validate_solution_function is not None or (lm is not None and not lm.on_device):
+            raise ValueError("%s: a language model walked on the host or a validate_solution_function put the host inside every "
+                             "position, one utterance at a time, from host recordings: use beam_search_batch" % where)
+
+    def begin_staged(self, x, mask, max_lengths, eol_symbol, lengths=None, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
+                     stop_on="patience"):
+        """`begin_batch` for a batch that is already on the device: x (T,N,F), mask (T,N) (SpeechRecognizer.compute_contexts_staged).
+        A batch of one is again the single search with the kernels of the batched one (`force_merge`); with `lengths` (the frames of
+        every utterance, host integers) its encoder pass runs over its own frames without a mask, as `begin_batch` runs it."""
+        self._refuse_host_work(None, "begin_staged")
+        n = int(x.shape[1])
+        if len(max_lengths) != n or (lengths is not None and len(lengths) != n):
+            raise ValueError("begin_staged: %d utterances, %d length limits" % (n, len(max_lengths)))
+        if n == 1 and lengths is not None and 0 < int(lengths[0]) <= int(x.shape[0]):
+            x, mask = x[: int(lengths[0])], None
+        return self._begin(lambda: self.rec.compute_contexts_staged(x, mask), max_lengths, eol_symbol, ignore_first_eol, char_discount,
+                           round_to_inf, stop_on, n == 1)
+
+    def search_staged(self, x, mask, max_lengths, eol_symbol, lengths=None, ignore_first_eol=False, char_discount=0, round_to_inf=1e9,
+                      stop_on="patience", as_arrays=False, validate_solution_function=None):
+        """`search_batch` over a staged batch -> list of N results or exceptions.  The fallbacks of `search_batch` are refusals here."""
+        self._refuse_host_work(validate_solution_function, "search_staged")
+        run = self.begin_staged(x, mask, max_lengths, eol_symbol, lengths=lengths, ignore_first_eol=ignore_first_eol,
+                                char_discount=char_discount, round_to_inf=round_to_inf, stop_on=stop_on)
+        while not run.done:
+            self.advance(run, POLL_EVERY, wait=True)
+        return self.finish_batch(run, as_arrays=as_arrays)
+
     def _begin(self, compute_contexts, limits, eol_symbol, ignore_first_eol, char_discount, round_to_inf, stop_on, force_merge,
                stepping=False):
         """`stepping`: the host drives every position itself (`_search_stepping`); it takes no looks through a pinned block."""

@@ -724,6 +724,26 @@ int lvsr_fbank_batch(void* stream, const short* wav, const long long* wav_off, c
 /* deltas + CMVN over the same set: edge frames replicated per utterance */
 int lvsr_add_deltas_cmvn_batch(void* stream, const float* feats, const int* frame_off, int n, int total_frames, int dim, const float* mean,
                                const float* istd, float* out);
+/* The recognizer's input batch from the packed static features of lvsr_fbank_batch in ONE launch: deltas, CMVN, the switch to
+ * time-major and the padding, which decoding otherwise does on the host (SpeechRecognizer._pad_recordings) behind a copy back.
+ *   feats (total_frames, dim), frame_off (n + 1) as above; with_deltas 0 / 1; W = 3 dim with deltas, dim without;
+ *   mean, istd (W) or both NULL; max_frames = the longest utterance's frames as the host counted them (lvsr_fbank_num_frames);
+ *   T >= max_frames the padded length (a shorter T is refused);  x (T, n, W), mask (T, n) float32 out.
+ * t < len_b: x[t, b, :] has the bits lvsr_add_deltas_cmvn_batch writes for that frame ([static | delta | delta-delta], edge frames
+ * replicated per utterance, (v - mean) * istd: one element function serves both kernels; without deltas (v - mean) * istd of the static
+ * row) and mask[t, b] = 1.  t >= len_b: the row is +0.0f and mask 0 — the kernel writes EVERY element of both outputs, so they may
+ * hold anything on entry; an utterance of no frames is an all-zero column.  dim <= 64, n <= 65535.  The grid (tiles of 56 frames x
+ * utterances) depends on T and n alone, no atomics: the launch can be captured.  The kernel stays inside its buffers whatever
+ * frame_off holds (an utterance is cut at T; offsets outside [0, total_frames] or out of order give an empty column). */
+int lvsr_frontend_batch(void* stream, const float* feats, const int* frame_off, int n, int total_frames, int max_frames, int dim,
+                        int with_deltas, const float* mean, const float* istd, int T, float* x, float* mask);
+/* Column sums for global CMVN (Normalization of lvsr/preprocessing.py:13-35): x (rows, width) contiguous float32, width <= 256;
+ *   sums[j] = sum_r x[r, j],  sums[width + j] = sum_r x[r, j]^2   (accumulate != 0: added to what sums holds),
+ * both in float64, the square taken in float64 (exact for a float32 value).  Two stages: min(1024, ceil(rows / 64)) work-groups over
+ * equal runs of rows write `partials` (scratch: 2 * width * 1024 doubles), a second launch adds the parts of every sum (64 strided runs in
+ * part order, then a fixed tree).  No
+ * atomics: every order depends on (rows, width) alone, so two runs give the same bits.  rows = 0 adds nothing. */
+int lvsr_feature_stats(void* stream, const float* x, long long rows, int width, double* partials, double* sums, int accumulate);
 
 /* ---- minibatch assembly from a device-resident training set -------------------------------------------
  * fuel Padding (libs/fuel/fuel/transformers/__init__.py:691-720) + the switch of the first two axes + ForceCContiguous of the
