@@ -2,6 +2,8 @@
 // reductions on the device: the alignment penalty and entropy, min / max / mean |x| of a tensor, per-parameter norms of a step.
 // They run behind the backward pass inside the step's graph region; the host copies a record of a few dozen numbers.
 // lvsr_utterance_stats is the decode report's share (lvsr/main.py:732-736, 778-790, 816-823): cost, alignment spread and penalty per utterance.
+// lvsr_alignment_times turns every label's alignment row into positions (peak, mean, quantiles of the running sum): what the reference
+// shows as a picture (show_alignment, lvsr/notebook.py:81, lvsr/main.py:834-840) as numbers a caller can turn into seconds.
 //
 // Determinism: no floating-point atomics.  Every kernel pair is "fixed slices -> partials, one work-group adds the partials": the
 // slices and the trees depend on the sizes alone, so eager launches, captured launches and graph replays give the same bits.
@@ -11,6 +13,7 @@
 // the reference monitors the parameter the gradient was taken at, and the optimiser overwrites it.
 #include "common.h"
 #include "lvsr_hip.h"
+#include <limits.h>
 #include <math.h>
 #include <string.h>
 
@@ -166,6 +169,84 @@ __global__ __launch_bounds__(64) void obs_utt_sum_kernel(const double* partials,
         for (int k = 0; k < 4; ++k) out[4 * (size_t)b + k] = s[k];
 }
 
+// ---- per-label alignment times (recognising with time stamps) -------------------------------------------------------------------
+// the smallest index over the wave (lanes that found none hold INT_MAX)
+__device__ __forceinline__ int obs_wave_min_int(int v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+// one wave per row (l,b), over n = lengths[b] (NULL: T') positions: out[8 row + k] = peak, w[peak], E1, sqrt(max(E2 - E1^2, 0)),
+// start, end, C[n-1], cost (include/lvsr_hip.h).  Two walks over the row with the same float32 scan (so the same bits): the first
+// finds the peak, the moments and C[n-1], the second the first positions at which C reaches lo C[n-1] and hi C[n-1].  A row whose
+// mask is 0 or whose n is 0 writes eight zeros and reads neither weights nor costs.
+__global__ __launch_bounds__(OBS_THREADS) void obs_align_times_kernel(const float* w, long long ldw, int rows, int B, int Tp, const float* mask,
+                                                                      const float* costs, const int* lengths, float lo, float hi, double* out8) {
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    if (row >= rows) return;
+    double* out = out8 + 8 * (size_t)row;
+    const float m = mask ? mask[row] : 1.f;
+    int n = lengths ? lengths[row % B] : Tp;
+    n = n < 0 ? 0 : n > Tp ? Tp : n;
+    if (m == 0.f || n == 0) {                              // (uniform over the wave)
+        if (lane < 8) out[lane] = 0.0;
+        return;
+    }
+    const float* cur = w + (size_t)row * ldw;
+    float carry = 0.f, best = -INFINITY;
+    int peak = INT_MAX;
+    double e1 = 0.0, e2 = 0.0;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int t = c0 + lane;
+        const float a = t < n ? cur[t] : 0.f;
+        const double at = (double)a * (double)t;           // exact while t < 2^29
+        e1 += at;
+        e2 += at * (double)t;
+        if (t < n && a > best) {                           // a lane meets its positions in rising order: `>` keeps the first
+            best = a;
+            peak = t;
+        }
+        carry = obs_last_lane(obs_wave_scan(a, lane) + carry, lane);       // lanes behind n add zeros: the last carry is C[n-1]
+    }
+    // (value, index) pairs through the xor tree: the larger value, on equal values the smaller index
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(peak, o, 64);
+        if (ov > best || (ov == best && oi < peak)) {
+            best = ov;
+            peak = oi;
+        }
+    }
+    e1 = obs_wave_sum_f64(e1);
+    e2 = obs_wave_sum_f64(e2);
+    const float total = carry, thr_lo = lo * total, thr_hi = hi * total;
+    int start = INT_MAX, end = INT_MAX;
+    carry = 0.f;
+    for (int c0 = 0; c0 < n; c0 += 64) {
+        const int t = c0 + lane;
+        const float s = obs_wave_scan(t < n ? cur[t] : 0.f, lane) + carry;
+        if (t < n && s >= thr_lo) start = min(start, t);
+        if (t < n && s >= thr_hi) end = min(end, t);
+        carry = obs_last_lane(s, lane);
+    }
+    start = obs_wave_min_int(start);
+    end = obs_wave_min_int(end);
+    if (lane == 0) {
+        // 0 <= lo, hi <= 1 and weights >= 0: C[n-1] itself reaches both thresholds.  Anything else (a NaN, negative weights) still
+        // gives positions inside the row.
+        out[0] = (double)(peak < n ? peak : 0);
+        out[1] = (double)best;
+        out[2] = e1;
+        out[3] = sqrt(fmax(e2 - e1 * e1, 0.0));
+        out[4] = (double)(start < n ? start : n - 1);
+        out[5] = (double)(end < n ? end : n - 1);
+        out[6] = (double)total;
+        out[7] = costs ? (double)costs[row] : 0.0;
+    }
+}
+
 // ---- min, max, sum |x| ----------------------------------------------------------------------------------------------------------
 // v = (min, max, sum): the tree of obs_block_sum with the three operations
 __device__ __forceinline__ void obs_block_mms(const double* v, double (*red)[OBS_THREADS]) {
@@ -306,6 +387,18 @@ int lvsr_utterance_stats(void* stream, const float* weights, long long ldw, int 
                        partials);
     hipLaunchKernelGGL(obs_utt_sum_kernel, dim3(B), dim3(64), 0, s, (const double*)partials, mask, L, B, out);
     return lvsr_check_launch("lvsr_utterance_stats");
+}
+
+int lvsr_alignment_times(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask, const float* costs,
+                         const int* lengths, float lo, float hi, double* out) {
+    LVSR_REQUIRE(weights && out, "lvsr_alignment_times: null argument");
+    LVSR_REQUIRE(L > 0 && B > 0 && Tp > 0 && ldw >= Tp, "lvsr_alignment_times: bad sizes (L, B, T' > 0; ldw >= T')");
+    LVSR_REQUIRE((long long)L * B <= (1ll << 30), "lvsr_alignment_times: more than 2^30 rows");
+    LVSR_REQUIRE(0.f <= lo && lo <= hi && hi <= 1.f, "lvsr_alignment_times: quantiles must satisfy 0 <= lo <= hi <= 1");       // (a NaN fails)
+    const int rows = L * B;
+    hipLaunchKernelGGL(obs_align_times_kernel, dim3((rows + 3) / 4), dim3(OBS_THREADS), 0, (hipStream_t)stream, weights, ldw, rows, B, Tp,
+                       mask, costs, lengths, lo, hi, out);
+    return lvsr_check_launch("lvsr_alignment_times");
 }
 
 int lvsr_tensor_stats(void* stream, const float* x, long long n, int use_floor, float floor, double* partials, double* out) {

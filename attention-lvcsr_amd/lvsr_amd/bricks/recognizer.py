@@ -444,6 +444,88 @@ class SpeechRecognizer(object):
             out[i][which].update(weights=W, energies=E)
         return out
 
+    # ---- alignment times (an addition: the reference shows alignments as pictures, lvsr/notebook.py:81) ----------------------------
+    @staticmethod
+    def _quantiles(quantiles):
+        lo, hi = (float(q) for q in quantiles)
+        if not 0.0 <= lo <= hi <= 1.0:
+            raise ValueError("quantiles must satisfy 0 <= lo <= hi <= 1, got (%r, %r)" % (lo, hi))
+        return lo, hi
+
+    def _align_contexts(self, encoded, encoded_mask, label_seqs, quantiles):
+        """The teacher-forced pass of `align_batch` / `align_staged` over contexts that are already computed: ONE
+        `cost_matrix(save_for_backward=False)` over the columns that have labels (gathered, as `analyze_batch` gathers the columns that
+        have a prediction: no all-masked column reaches the decoder kernels), ONE lvsr_alignment_times launch, ONE copy of L B 8
+        doubles — the only synchronisation.  Runs on the caller's stream.  -> list of (L_i, 8) float64 arrays."""
+        from ..observables import TIMES, alignment_times
+        lo, hi = quantiles
+        seqs = [[int(t) for t in s] for s in label_seqs]
+        if len(seqs) != int(encoded.shape[1]):
+            raise ValueError("%d label sequences for %d utterances" % (len(seqs), int(encoded.shape[1])))
+        out = [numpy.zeros((0, TIMES)) for _ in seqs]
+        cols = [i for i, s in enumerate(seqs) if s]
+        if not cols:
+            return out
+        gen, ws = self.generator, self.ws
+        y, ym = self._pad_labels([seqs[i] for i in cols])
+        yb, ymb = self._t(y, torch.int64, "labels"), self._t(ym, torch.float32, "labels_mask")
+        if len(cols) != len(seqs):
+            idx = torch.tensor(cols, dtype=torch.int64).to(self.device, non_blocking=True)
+            encoded, encoded_mask = encoded.index_select(1, idx), encoded_mask.index_select(1, idx)
+        lengths = encoded_mask.sum(dim=0).to(torch.int32)
+        cm = gen.cost_matrix(yb, ymb, attended=encoded, attended_mask=encoded_mask, save_for_backward=False)
+        record = ws.get("align.times", tuple(cm.shape) + (TIMES,), torch.float64)
+        alignment_times(self.lib, gen.last["weights"], ymb, cm, record, lengths=lengths, lo=lo, hi=hi)
+        host = record.cpu().numpy()                           # the one synchronisation
+        for j, i in enumerate(cols):
+            out[i] = host[: len(seqs[i]), j].copy()
+        return out
+
+    def align_batch(self, recordings, label_seqs, pad_to=64, quantiles=(0.1, 0.9)):
+        """Where on the attended axis every label of every utterance sits: `recordings` a list of (T_i, F) arrays, `label_seqs` a list
+        of label sequences (ground truths for forced alignment, hypotheses for time stamps) -> a list of (L_i, 8) float64 arrays, the
+        rows of lvsr_alignment_times (include/lvsr_hip.h; `observables.PEAK` .. `COST`): peak position, weight there, mean position,
+        spread, the positions at which the running sum of the alignment reaches quantiles[0] and quantiles[1] of its total, the
+        total, the label's cost.  Positions count attended (subsampled) frames: `decode.token_times` turns them into seconds.
+        Padded as `analyze_batch` pads; ONE encoder pass, ONE teacher-forced `cost_matrix(save_for_backward=False)` pass, one
+        lvsr_alignment_times launch, one copy of L B 8 doubles — the only synchronisation; nothing of the (L,B,T') alignment leaves the
+        device.  An empty label sequence gives a (0,8) array (its column is gathered out in front of the decoder pass).  Under an mse
+        criterion the labels are their own ground truth; with a language model attached the cost is the fused one, as in `analyze`."""
+        quantiles = self._quantiles(quantiles)
+        if len(recordings) == 0:
+            return []
+        if len(label_seqs) != len(recordings):
+            raise ValueError("align_batch: %d recordings, %d label sequences" % (len(recordings), len(label_seqs)))
+        x, xm = self._pad_recordings(recordings, pad_to)
+        with self._on_stream():
+            xb, xmb = self._t(x, torch.float32, "recordings"), self._t(xm, torch.float32, "recordings_mask")
+            encoded, encoded_mask = self.encoder.apply(self.bottom.apply(xb, False), xmb, save_for_backward=False)
+            return self._align_contexts(encoded, encoded_mask, label_seqs, quantiles)
+
+    def align_staged(self, x, mask, lengths, label_seqs, quantiles=(0.1, 0.9), reuse_contexts=False):
+        """`align_batch` over a batch that is already on the device (`frontend.FrontEnd.batch`): x (T,B,F), mask (T,B), `lengths` the
+        frames of every utterance (host integers).  The argument checks of `compute_contexts_staged`; the features are not copied.  As
+        `BeamSearch.begin_staged` does, a batch of one runs over its own frames without a mask — so what is aligned here is what a
+        staged search of the same batch saw.
+        `reuse_contexts`: no encoder pass; the teacher-forced pass reads the contexts that this recognizer's last
+        `compute_contexts_staged` made from this very x and mask (the staged search of the chunk: `decode.recognize(timestamps=True)`)
+        — refused when that call saw other tensors; that they still hold the same values is the caller's word."""
+        quantiles = self._quantiles(quantiles)
+        self._check_staged(x, mask, "align_staged")
+        B = int(x.shape[1])
+        if len(lengths) != B or len(label_seqs) != B:
+            raise ValueError("align_staged: %d utterances, %d lengths, %d label sequences" % (B, len(lengths), len(label_seqs)))
+        if B == 1 and 0 < int(lengths[0]) <= int(x.shape[0]):
+            x, mask = x[: int(lengths[0])], None
+        with self._on_stream():
+            if reuse_contexts:
+                if getattr(self, "_staged", None) is None or self._staged[0] != self._staged_key(x, mask):
+                    raise ValueError("align_staged: reuse_contexts, but the last compute_contexts_staged call saw other tensors")
+                encoded, encoded_mask = self._staged[1:]
+            else:
+                encoded, encoded_mask = self._encode_staged(x, mask, "align_staged")
+            return self._align_contexts(encoded, encoded_mask, label_seqs, quantiles)
+
     # ---- decoding (recognizer.py:496-533) ------------------------------------------------------------
     def compute_contexts(self, recordings):
         """Encoder at batch 1 with NO input mask (init_beam_search builds the graph with use_mask=False,
@@ -478,18 +560,31 @@ class SpeechRecognizer(object):
         """The encoder pass of `compute_contexts_batch` over a batch that is already on the device (`frontend.FrontEnd.batch`):
         x (T,B,F) float32, mask (T,B) float32 — or None: no input mask, as `compute_contexts` runs a single utterance.  No copy: the
         tensors are read where they are, so they must keep their values until the searches that use the contexts have begun."""
+        encoded, encoded_mask = self._encode_staged(x, mask, "compute_contexts_staged")
+        # what `align_staged(reuse_contexts=True)` teacher-forces over: the contexts, and which tensors they were made from
+        self._staged = (self._staged_key(x, mask), encoded, encoded_mask)
+        self.generator.init_generation(encoded, encoded_mask)
+
+    @staticmethod
+    def _staged_key(x, mask):
+        return (x.data_ptr(), tuple(x.shape), None if mask is None else (mask.data_ptr(), tuple(mask.shape)))
+
+    def _encode_staged(self, x, mask, where):
+        """The argument checks and the encoder pass of the staged entry points -> (encoded, encoded_mask)."""
+        self._check_staged(x, mask, where)
+        return self.encoder.apply(self.bottom.apply(x, False), mask, save_for_backward=False)
+
+    def _check_staged(self, x, mask, where):
         tensors = [("x", x, 3)] + ([("mask", mask, 2)] if mask is not None else [])
         for name, t, nd in tensors:
             if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != nd or not t.is_contiguous():
-                raise ValueError("compute_contexts_staged: %s must be a contiguous float32 tensor of %d dimensions" % (name, nd))
+                raise ValueError("%s: %s must be a contiguous float32 tensor of %d dimensions" % (where, name, nd))
             if t.device.type != self.device.type or (self.device.index is not None and t.device.index != self.device.index):
-                raise ValueError("compute_contexts_staged: %s lives on %s, the recognizer on %s" % (name, t.device, self.device))
+                raise ValueError("%s: %s lives on %s, the recognizer on %s" % (where, name, t.device, self.device))
         if int(x.shape[2]) != self.d.F:
-            raise ValueError("compute_contexts_staged: %d features per frame, the recognizer takes %d" % (x.shape[2], self.d.F))
+            raise ValueError("%s: %d features per frame, the recognizer takes %d" % (where, x.shape[2], self.d.F))
         if mask is not None and tuple(mask.shape) != tuple(x.shape[:2]):
-            raise ValueError("compute_contexts_staged: mask %s for recordings %s" % (tuple(mask.shape), tuple(x.shape)))
-        encoded, encoded_mask = self.encoder.apply(self.bottom.apply(x, False), mask, save_for_backward=False)
-        self.generator.init_generation(encoded, encoded_mask)
+            raise ValueError("%s: mask %s for recordings %s" % (where, tuple(mask.shape), tuple(x.shape)))
 
     def beam_search_staged(self, x, mask, lengths, **kwargs):
         """`beam_search_batch` for a batch staged on the device: x (T,B,F), mask (T,B), `lengths` the frames of every utterance (a

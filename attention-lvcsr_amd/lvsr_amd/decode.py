@@ -149,24 +149,92 @@ def recognize_plan(num_samples, batch, sort=True):
     return [order[i: i + batch] for i in range(0, len(order), batch)]
 
 
-def recognize(recognizer, front_end, waveforms, beam_size=10, batch=64, char_discount=0.0, round_to_inf=1e9, stop_on="patience",
-              to_text=None, sort=True):
-    """From waveforms to hypotheses: `waveforms` is a sequence of 1-D int16 arrays or of (id, array) pairs (ids default to the
-    position); `front_end` a `frontend.FrontEnd`.  Each chunk of `recognize_plan` goes through FrontEnd.batch (two launches; the PCM
-    is all that is copied to the device) and SpeechRecognizer.beam_search_staged.  -> one row per utterance IN INPUT ORDER:
-    dict(id=, recognized=, search_cost=, num_frames=) and text= when `to_text(labels)` is given; an utterance whose search finds no
-    candidate has recognized=[], search_cost=nan and error="CandidateNotFoundError", as in `search`."""
+def token_times(rows, labels, subsample, frame_shift, frame_length, sample_rate, num_frames, mse=False):
+    """Alignment rows to seconds (pure host arithmetic): `rows` (L,8) as `SpeechRecognizer.align_batch` returns them for one
+    utterance, `labels` its L labels, `subsample` the encoder's per-layer factors, `frame_shift` / `frame_length` in samples,
+    `num_frames` the utterance's frames -> a list of dict(label=, start=, end=, peak=, confidence=), times in seconds.
+    With S = prod(subsample): the reference's encoder takes [::k] behind every layer (lvsr/bricks/__init__.py:75-77), so attended position p
+    stands for the input frames from p S on, and
+      start = start_pos S shift,   end = min((end_pos + 1) S shift, duration),   peak = the middle of the span of peak_pos,
+    all clipped to duration = ((num_frames - 1) frame_shift + frame_length) / sample_rate.  The times are NOMINAL: the contexts come
+    out of a bidirectional network that has seen the whole utterance, so a position covers its S frames only by construction.
+    confidence = exp(-cost), the probability the model gave the label (with a language model attached: the fused one).  `mse`: under
+    an mse criterion the cost is a squared error, not a log-probability, so the key is left out."""
+    rows = numpy.asarray(rows, numpy.float64).reshape(-1, 8)
+    if len(rows) != len(labels):
+        raise ValueError("token_times: %d rows for %d labels" % (len(rows), len(labels)))
+    span = float(numpy.prod([int(k) for k in subsample])) * float(frame_shift) / float(sample_rate)
+    duration = ((int(num_frames) - 1) * float(frame_shift) + float(frame_length)) / float(sample_rate)
+    out = []
+    for label, r in zip(labels, rows):
+        token = dict(label=int(label), start=min(float(r[4]) * span, duration), end=min((float(r[5]) + 1.0) * span, duration),
+                     peak=min((float(r[0]) + 0.5) * span, duration))
+        if not mse:
+            token["confidence"] = float(numpy.exp(-r[7]))
+        out.append(token)
+    return out
+
+
+def group_words(tokens, word_boundary):
+    """Tokens of `token_times` to words: `word_boundary` is a set of labels (space, EOS, ...); a word is a run of tokens that are
+    not in it -> a list of dict(labels=, start=, end=, confidence=): start of its first token, end of its last, the smallest token
+    confidence (absent when the tokens carry none).  Boundary tokens belong to no word."""
+    boundary = set(int(b) for b in word_boundary)
+    words, run = [], []
+
+    def close():
+        if run:
+            word = dict(labels=[t["label"] for t in run], start=run[0]["start"], end=run[-1]["end"])
+            if all("confidence" in t for t in run):
+                word["confidence"] = min(t["confidence"] for t in run)
+            words.append(word)
+            del run[:]
+    for t in tokens:
+        if t["label"] in boundary:
+            close()
+        else:
+            run.append(t)
+    close()
+    return words
+
+
+def _waveform_items(recognizer, front_end, waveforms, where):
+    """[(id, samples)], their sample counts — behind the refusals `recognize` and `align` share"""
     items = []
     for number, w in enumerate(waveforms):
         ident, samples = w if isinstance(w, tuple) else (number, w)
         items.append((ident, samples))
     if front_end.num_features != recognizer.d.F:
-        raise ValueError("recognize: the front end makes %d features per frame, the recognizer takes %d" % (front_end.num_features, recognizer.d.F))
+        raise ValueError("%s: the front end makes %d features per frame, the recognizer takes %d" % (where, front_end.num_features, recognizer.d.F))
     num_samples = [int(len(s)) for _, s in items]
-    frames = [front_end.num_frames(n) for n in num_samples]
-    for (ident, _), n, f in zip(items, num_samples, frames):
-        if f <= 0:
-            raise ValueError("recognize: utterance %r has %d samples, fewer than one frame (%d samples)" % (ident, n, front_end.fbank.frame_length))
+    for (ident, _), n in zip(items, num_samples):
+        if front_end.num_frames(n) <= 0:
+            raise ValueError("%s: utterance %r has %d samples, fewer than one frame (%d samples)" % (where, ident, n, front_end.fbank.frame_length))
+    return items, num_samples
+
+
+def _timed(recognizer, front_end, row, rows8, labels, word_boundary):
+    """adds tokens= (and words=) to `row` from the alignment rows of its labels"""
+    fb = front_end.fbank
+    row["tokens"] = token_times(rows8, labels, recognizer.d.subsample, fb.frame_shift, fb.frame_length, front_end.sample_rate,
+                                row["num_frames"], mse=recognizer.generator.mse)
+    if word_boundary is not None:
+        row["words"] = group_words(row["tokens"], word_boundary)
+
+
+def recognize(recognizer, front_end, waveforms, beam_size=10, batch=64, char_discount=0.0, round_to_inf=1e9, stop_on="patience",
+              to_text=None, sort=True, timestamps=False, quantiles=(0.1, 0.9), word_boundary=None):
+    """From waveforms to hypotheses: `waveforms` is a sequence of 1-D int16 arrays or of (id, array) pairs (ids default to the
+    position); `front_end` a `frontend.FrontEnd`.  Each chunk of `recognize_plan` goes through FrontEnd.batch (two launches; the PCM
+    is all that is copied to the device) and SpeechRecognizer.beam_search_staged.  -> one row per utterance IN INPUT ORDER:
+    dict(id=, recognized=, search_cost=, num_frames=) and text= when `to_text(labels)` is given; an utterance whose search finds no
+    candidate has recognized=[], search_cost=nan and error="CandidateNotFoundError", as in `search`.
+    `timestamps` (an addition): every row also carries tokens= (`token_times` of its recognised labels; [] where no candidate was
+    found) and, with `word_boundary` (a set of labels), words= (`group_words`).  Behind a chunk's search its best hypotheses are
+    aligned by one `SpeechRecognizer.align_staged` call that teacher-forces over the contexts the search was started from — no second
+    encoder pass —, one lvsr_alignment_times launch and one small copy per chunk; `quantiles` are the shares of a label's alignment
+    mass at which it starts and ends.  Without `timestamps` the launches and the rows are what they were."""
+    items, num_samples = _waveform_items(recognizer, front_end, waveforms, "recognize")
     recognizer.init_beam_search(beam_size)
     kw = dict(char_discount=char_discount, round_to_inf=round_to_inf, stop_on=stop_on)
     rows = [None] * len(items)
@@ -183,4 +251,30 @@ def recognize(recognizer, front_end, waveforms, beam_size=10, batch=64, char_dis
             if to_text is not None:
                 row["text"] = to_text(row["recognized"])
             rows[i] = row
+        if timestamps:
+            best = [rows[i]["recognized"] for i in chunk]
+            for i, rows8 in zip(chunk, recognizer.align_staged(x, mask, lengths, best, quantiles=quantiles, reuse_contexts=True)):
+                _timed(recognizer, front_end, rows[i], rows8, rows[i]["recognized"], word_boundary)
+    return rows
+
+
+def align(recognizer, front_end, waveforms, transcripts, batch=64, quantiles=(0.1, 0.9), word_boundary=None, sort=True):
+    """Forced alignment: when was each label of a GIVEN label sequence said.  `waveforms` as for `recognize`, `transcripts` one label
+    sequence per waveform (as the recognizer was trained on them: with EOS where the data had it).  Chunks of `recognize_plan`, each
+    through FrontEnd.batch and one `SpeechRecognizer.align_staged` call (one encoder pass, one teacher-forced pass, one
+    lvsr_alignment_times launch, one small copy).  -> one row per utterance IN INPUT ORDER: dict(id=, num_frames=, cost= the summed
+    cost of the labels, tokens=) and words= when `word_boundary` is given (`token_times`, `group_words`).  The refusals of `recognize`
+    — another feature width, an utterance shorter than one frame —, and a `transcripts` of another length than `waveforms`."""
+    waveforms = list(waveforms)
+    transcripts = [[int(t) for t in s] for s in transcripts]
+    if len(transcripts) != len(waveforms):
+        raise ValueError("align: %d waveforms, %d transcripts" % (len(waveforms), len(transcripts)))
+    items, num_samples = _waveform_items(recognizer, front_end, waveforms, "align")
+    rows = [None] * len(items)
+    for chunk in recognize_plan(num_samples, batch, sort):
+        x, mask, lengths = front_end.batch([items[i][1] for i in chunk])
+        aligned = recognizer.align_staged(x, mask, lengths, [transcripts[i] for i in chunk], quantiles=quantiles)
+        for i, n, rows8 in zip(chunk, lengths, aligned):
+            rows[i] = dict(id=items[i][0], num_frames=int(n), cost=float(rows8[:, 7].sum()))
+            _timed(recognizer, front_end, rows[i], rows8, transcripts[i], word_boundary)
     return rows

@@ -82,6 +82,25 @@ def utterance_stats(lib, weights, mask, costs, out, ws, lengths=None):
              ptr(lengths), ptr(partials), ptr(out))
 
 
+TIMES = 8                            # doubles per (l,b) row of lvsr_alignment_times
+PEAK, PEAK_WEIGHT, MEAN, SPREAD, START, END, MASS, COST = range(TIMES)
+
+
+def alignment_times(lib, weights, mask, costs, out, lengths=None, lo=0.1, hi=0.9):
+    """Enqueue lvsr_alignment_times on weights (L,B,T') — rows may be strided views of a larger buffer —, mask / costs (L,B) or
+    None, lengths (B) int32 or None (each utterance's own attended length), into `out` (L,B,8) float64: per label the peak position,
+    the weight there, the mean position, the spread, the positions at which the running sum reaches `lo` and `hi` of its total, the
+    total, and the label's cost (the slots PEAK .. COST above)."""
+    L, B, Tp = (int(s) for s in weights.shape)
+    assert weights.stride(2) == 1 and weights.stride(0) == B * weights.stride(1), "the (l,b) rows must be equally spaced"
+    for t in (mask, costs):
+        assert t is None or (t.is_contiguous() and tuple(t.shape) == (L, B) and t.dtype == torch.float32)
+    assert lengths is None or (lengths.is_contiguous() and tuple(lengths.shape) == (B,) and lengths.dtype == torch.int32)
+    assert out.is_contiguous() and tuple(out.shape) == (L, B, TIMES) and out.dtype == torch.float64
+    lib.call("lvsr_alignment_times", lib.stream_for(out), ptr(weights), int(weights.stride(1)), L, B, Tp, ptr(mask), ptr(costs),
+             ptr(lengths), float(lo), float(hi), ptr(out))
+
+
 def tensor_stats(lib, x, out, ws, floor=None):
     """Enqueue lvsr_tensor_stats on the contiguous tensor x into the three doubles of `out` (min, max, sum |x|)."""
     assert x.is_contiguous() and x.dtype == torch.float32

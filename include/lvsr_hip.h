@@ -516,6 +516,26 @@ int lvsr_alignment_stats(void* stream, const float* weights, long long ldw, int 
  * depends on the sizes alone, so two runs give the same bits. */
 int lvsr_utterance_stats(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask,
                          const float* costs, const int* lengths, double* partials, double* out);
+/* Alignment times per label: where on the attended axis each label's alignment row sits, for time stamps (the reference shows the
+ * rows as a picture: show_alignment, lvsr/notebook.py:81).  weights, ldw, mask, costs, lengths as for lvsr_utterance_stats (rows may
+ * be strided views; n_b = lengths[b] clamped to [0, T'], NULL: T'; what lies behind n_b is padding and is not read).  lo, hi: the
+ * quantiles, 0 <= lo <= hi <= 1.  out (L,B,8) float64; for a row with mask[l,b] != 0 and n = n_b > 0, with w = the row and
+ * C[t] = w[0] + ... + w[t] the kernel's float32 running sum (the 64-lane scan of lvsr_alignment_stats plus a carry between chunks):
+ *   out[l][b][0] = peak: the smallest t < n at which w[t] is largest (float32 comparison)
+ *   out[l][b][1] = w[peak] (the float32 value, held exactly)
+ *   out[l][b][2] = E1 = sum_{t<n} w[t] t
+ *   out[l][b][3] = sqrt(max(E2 - E1^2, 0)),  E2 = sum_{t<n} w[t] t^2          (both moments as lvsr_utterance_stats takes them)
+ *   out[l][b][4] = start: the smallest t with C[t] >= lo C[n-1]                (the product rounded to float32)
+ *   out[l][b][5] = end:   the smallest t with C[t] >= hi C[n-1]
+ *   out[l][b][6] = C[n-1]
+ *   out[l][b][7] = costs[l,b]                                                  (costs NULL: 0)
+ * A row whose mask is 0, or whose n_b is 0, writes eight zeros and reads neither weights nor costs.  For non-negative weights
+ * C[n-1] reaches both thresholds, so start <= end <= n - 1; a row that holds a NaN or negative weights still gets positions in
+ * [0, n - 1].  One wave per row (l,b), four rows per work-group; the row is walked twice with the same scan (the thresholds need
+ * C[n-1] first; the second walk hits the cache), the argmax is an xor tree over (value, index) pairs that keeps the smaller index on
+ * equal values, the moments are float64 per lane folded by the xor tree.  No scratch buffer, no atomics: two runs give the same bits. */
+int lvsr_alignment_times(void* stream, const float* weights, long long ldw, int L, int B, int Tp, const float* mask,
+                         const float* costs, const int* lengths, float lo, float hi, double* out);
 /* out[0] = min, out[1] = max (both exact; float32 values held in doubles), out[2] = sum |x| over the n contiguous floats of x;
  * use_floor != 0: over max(x, floor) instead (the gain matrix as RewardRegressionEmitter.cost sees it, lvsr/bricks/__init__.py:154).
  * Two stages: ceil(n / 8192) work-groups (at most 1024: the grid depends on n only) with float64 sums per thread and a fixed
